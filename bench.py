@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — LiDAR frames/s (forward + backward) of the voxel-backbone hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]          (N>1: launched by torch.distributed.run)
 
 One step = one pass of the hot path over one batch of synthetic frames that are already resident
 in HBM as raw points: device voxelization (+fused reader) -> 8 rulebooks -> SpMiddleResNetFHD
@@ -11,16 +11,22 @@ grad-clip(35) -> Adam (true weight decay, OneCycle schedule: the reference's fas
 Default workload = north_star's target: CenterPoint-voxelnet + S2D (`KD_VoxelNet` student: S2D
 densify module + PCR head + RPN trunk + CenterHead), forward + backward, B=4 frames per GPU of the
 150k-point 0.1 m-voxel synthetic Waymo scene.  `--workload centerpoint` = BASELINE configs[1],
-`--workload s2d_distill` = configs[2] (teacher + student dual forward); at N=1 both are also timed
-(short) and reported under `other_workloads` of the same JSON line.
+`--workload s2d_distill` = configs[2] (teacher + student dual forward); with --full at N=1 both are also
+timed (short) and reported under `other_workloads` of the same JSON line.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), config and
+step_breakdown (the chosen execution mode, per-step event times).  A plain run does only that; --full adds:
+  step_breakdown.kernel_ms_per_step : a torch.profiler pass over two more steps
+  config.scene : voxels, active sites and pairs per stage of the benchmark scene
+  other_workloads : the other configurations / precisions, timed short (N=1)
   roofline     : the dominant hand-written kernel of the step by total time (per-launch HIP events)
   sparse_gemm  : MFMA fraction of the sparse implicit GEMM at C >= 64 (forward + data gradient)
   rulebook     : HBM fraction of the rulebook stage (4 SubM + 4 strided builds per backbone pass, one launch chain since r04)
   voxelize     : HBM fraction of the device voxelizer chains (20 B per point + 116 B per voxel)
   cpu_baseline : the CPU oracle stack on a bounded sample (150k-pt frame, and BASELINE configs[0]:
                  SECOND on the 8k-pt cloud, 3 warm-up + 10 timed iterations, median), host cores stated
+--dump-outputs DIR writes what the last timed step computed (dump_outputs below); the inputs (resident frames, initial weights) are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -83,6 +89,11 @@ def parse():
     p.add_argument("--no-breakdown", action="store_true", help="skip the torch.profiler kernel-time pass of step_breakdown")
     p.add_argument("--no-graph", action="store_true", help="launch the dense segment (neck + head + losses) kernel by kernel from Python "
                    "instead of replaying it as two HIP graphs per step (sparse2dense_amd/graphed.py)")
+    p.add_argument("--full", action="store_true", help="after the headline: the kernel-time pass of step_breakdown, scene sizes, roofline / "
+                   "sparse_gemm / rulebook / voxelize, other_workloads and cpu_baseline (each can still be dropped with its --no-* option).  "
+                   "Default: the headline only (set up, pick the mode, warm up, time the steps)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last timed step computed "
+                   "(loss, gradient norm, a fixed sample of the updated parameters, of their gradients and of the batch-norm buffers) as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -569,6 +580,32 @@ def stats_top_kernels():
     return names, "profiles/" + os.path.basename(files[0])
 
 
+DUMP_SAMPLE = 1 << 22   # values kept per concatenated vector (16 MB in float32)
+
+
+def dump_outputs(out_dir, model, loss, grad_norm):
+    """what the last timed step handed its caller, as out_dir/<name>.npy: loss and total gradient norm (float64, shape [1]); the
+    trainable parameters after the update, their gradients and the float buffers (batch-norm running statistics), each concatenated
+    in name order (float32) and, when longer than DUMP_SAMPLE, sampled at fixed indices drawn from a seeded generator"""
+    os.makedirs(out_dir, exist_ok=True)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    vectors = dict(
+        params=[p.detach().float().reshape(-1) for _, p in named],
+        grads=[(torch.zeros_like(p) if p.grad is None else p.grad).detach().float().reshape(-1) for _, p in named],
+        buffers=[b.detach().float().reshape(-1) for _, b in sorted(model.named_buffers()) if b.is_floating_point()])
+    for name, parts in vectors.items():
+        if not parts:
+            continue
+        v = torch.cat(parts)
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(20240928).integers(0, v.numel(), DUMP_SAMPLE))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), v.cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.detach().item())], np.float64))
+    if grad_norm is not None:
+        np.save(os.path.join(out_dir, "grad_norm.npy"), np.array([float(grad_norm.detach().item())], np.float64))
+
+
 def _build_info():
     try:
         from sparse2dense_amd import _lib
@@ -824,7 +861,7 @@ def main():
     detail = {}
     elapsed, loss = timed(run_step, args.steps, args.warmup, world, dev, detail)
     graph_stats = dict(graphed.stats)
-    grad_norm = None
+    grad_norm = ln = None
     if step.last_norm is not None or run_step.last_norm is not None:
         ln = run_step.last_norm if run_step.last_norm is not None else step.last_norm
         grad_norm = float(ln.item())
@@ -832,7 +869,9 @@ def main():
         # finite is not that step (r03/r04 timed one for a round and a half: DESIGN rule 31)
         assert np.isfinite(grad_norm), f"bench.py: gradient norm of the last timed step is {grad_norm}"
     assert np.isfinite(float(loss.item())), "bench.py: loss of the last timed step is not finite"
-    if rank == 0 and world == 1 and not args.no_breakdown:
+    if args.dump_outputs and rank == 0:   # before anything below runs another step
+        dump_outputs(args.dump_outputs, getattr(model, "module", model), loss, ln)
+    if rank == 0 and world == 1 and args.full and not args.no_breakdown:
         detail.update(kernel_time_per_step(run_step) or {})
         if "device_busy_ms_per_step" in detail:   # what the step spends with NO kernel running anywhere on the device: the host's share
             detail["ms_per_step_minus_device_busy_ms"] = round(elapsed / args.steps * 1e3 - detail["device_busy_ms_per_step"], 3)
@@ -856,14 +895,14 @@ def main():
     if hasattr(frames, "close"):   # loader thread of the timed run: done (the passes below build their examples inside the step)
         frames.close()
         frames = frames.frames
-    stats = scene_stats(model, frames) if rank == 0 else {}
+    stats = scene_stats(model, frames) if (rank == 0 and args.full) else None
     roof, rows, rulebook, sparse_gemm, voxelize, roofline_wgrad = (None, [], None, None, None, None)
-    if single and not args.no_roofline:
+    if single and args.full and not args.no_roofline:
         roof, rows, rulebook, sparse_gemm, voxelize, roofline_wgrad = roofline_pass(step.sync_step)
     loss_value = round(float(loss.item()), 4)
 
     others = {}
-    if single and not args.no_extras and not args.workload.startswith("pillar"):
+    if single and args.full and not args.no_extras and not args.workload.startswith("pillar"):
         import copy
         del model, teacher, frames, step
         torch.cuda.empty_cache()
@@ -942,7 +981,7 @@ def main():
             os.environ.pop("S2D_FORCE_DDP", None)
             set_mode([], mode)
     base = None
-    if single and not args.no_cpu_baseline:
+    if single and args.full and not args.no_cpu_baseline:
         base = cpu_baseline_subprocess(args)
 
     if rank == 0:
@@ -971,10 +1010,12 @@ def main():
                        "library": _build_info(),
                        "dense_segment": ("HIP graphs (sparse2dense_amd/graphed.py): neck + head + losses forward / backward = 2 graph launches per step; "
                                          + str(graph_stats) if graph_stats and graph_stats.get("replay") else "launched kernel by kernel"),
-                       "loss": loss_value, "scene": stats},
+                       "loss": loss_value},
             "step_breakdown": detail,
-            "roofline": roof, "roofline_wgrad": roofline_wgrad, "sparse_gemm": sparse_gemm, "rulebook": rulebook, "voxelize": voxelize, "cpu_baseline": base,
         }
+        if args.full:
+            out["config"]["scene"] = stats
+            out.update(roofline=roof, roofline_wgrad=roofline_wgrad, sparse_gemm=sparse_gemm, rulebook=rulebook, voxelize=voxelize, cpu_baseline=base)
         if others:
             out["other_workloads"] = others
         if rows:

@@ -10,7 +10,7 @@ if [ -z "$SKIP_TESTS" ]; then
 timeout 3000 python -m pytest tests -m gpu -q --timeout 900 > $O/gpu_tests.log 2>&1 < /dev/null
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 < /dev/null
 fi
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err < /dev/null
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err < /dev/null
 cd /tmp && export TMPDIR=/tmp
 B="--no-breakdown --no-cpu-baseline --no-extras --no-roofline"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_s2d -- python $R/bench.py --mode eager:instep:0 --steps 6 --warmup 3 $B > $R/$O/prof_s2d.log 2>&1 < /dev/null
