@@ -109,6 +109,11 @@ class SingleStageDetector(nn.Module):
             seg = segs[name] = GraphedSegment(fn, mods, name=f"{type(self).__name__}.{name}")
         return seg
 
+    def _segments_busy(self):
+        """a segment of this model has a grad-mode replay that still awaits its backward (graphed.GraphedSegment.backward_pending): the padded
+        lists of `_padded_list`, which every segment of the model reads in place, must not be refilled"""
+        return any(seg.backward_pending() for seg in self.__dict__.get("_segments", {}).values())
+
     @staticmethod
     def _flat_targets(example, tasks):
         """the CenterHead targets of an example as a flat tensor list (task-major)"""
@@ -161,21 +166,27 @@ class SingleStageDetector(nn.Module):
             seg.__dict__["_spec"] = spec
         return self._unflat_struct(spec, list(outs))
 
-    def _padded_list(self, key, coors, feats):
+    def _padded_list(self, key, coors, feats, fresh=False):
         """a voxel list (coors [M,4] + feats [M,C]) in capacity-sized persistent buffers (rows past the list carry batch index -1, which every
         PCR kernel skips): a static-shaped input for the graph, whatever the cloud's voxel count.  The copies of all lists of a step go out in
-        one multi-tensor launch (`_flush_recon`)."""
+        one multi-tensor launch (`_flush_recon`).  fresh: a replay that still awaits its backward reads the persistent buffers
+        (`_segments_busy`) - new ones for this call."""
         coors = coors if coors.dtype == torch.int32 else coors.int()
         feats = feats.float()
         m = int(coors.shape[0])
         store = self.__dict__.setdefault("_recon_pad", {})
         ent = store.get(key)
-        if ent is None or ent[0].shape[0] < m or ent[0].device != coors.device or ent[1].shape[1] != feats.shape[1]:
+        if ent is None or ent[0].shape[0] < m or ent[0].device != coors.device or ent[1].shape[1] != feats.shape[1] or fresh:
             cap = -(-int(m * 1.5 + 1) // 65536) * 65536
+            if fresh and ent is not None and ent[0].shape[0] >= m:
+                cap = ent[0].shape[0]   # (the shape the persistent buffers have)
             cb = torch.full((cap, 4), -1, dtype=torch.int32, device=coors.device)
             fb = torch.zeros((cap, feats.shape[1]), dtype=torch.float32, device=coors.device)
-            cb._s2d_static = fb._s2d_static = True
-            ent = store[key] = [cb, fb, 0]
+            if fresh:   # the persistent buffers still feed a pending backward: this call gets lists of its own
+                ent = [cb, fb, 0]
+            else:
+                cb._s2d_static = fb._s2d_static = True
+                ent = store[key] = [cb, fb, 0]
         cb, fb, prev = ent
         pend = self.__dict__.setdefault("_recon_pending", ([], []))
         pend[0].extend([cb[:m], fb[:m]])
@@ -328,8 +339,8 @@ class KD_VoxelNet(VoxelNet):
         losses = self.bbox_head.loss(example, preds) if return_loss else None
         return losses, F_S_a, F_S_b, preds, mask_loss, comp_loss
 
-    def _padded_recon(self, example, scale):
-        return self._padded_list(scale, example[f"reconstruction_coordinates_{scale}"], self._read_scaled(example, scale))
+    def _padded_recon(self, example, scale, fresh=False):
+        return self._padded_list(scale, example[f"reconstruction_coordinates_{scale}"], self._read_scaled(example, scale), fresh)
 
     def _dense_part_s2d(self, x, example, want_pcr):
         """first half of `_dense_part` as a segment of its own: S2D module + PCR head + PCR losses -> (F_S_a, F_S_b, mask_loss, comp_loss)"""
@@ -359,8 +370,9 @@ class KD_VoxelNet(VoxelNet):
             tasks = len(self.bbox_head.tasks)
             tag = f"{int(torch.is_grad_enabled())}"
             recon = []
+            busy = self._segments_busy()
             for s_ in (4, 2):
-                recon += list(self._padded_recon(example, s_))
+                recon += list(self._padded_recon(example, s_, busy))
             self._flush_recon()
 
             def part_a(x_, c4, f4, c2, f2):
@@ -378,8 +390,9 @@ class KD_VoxelNet(VoxelNet):
             side = self._flat_targets(example, tasks) if return_loss else []
             nt = len(side)
             if want_pcr:
+                busy = self._segments_busy()
                 for s_ in (4, 2):
-                    side += list(self._padded_recon(example, s_))
+                    side += list(self._padded_recon(example, s_, busy))
                 self._flush_recon()
 
             def part(x_, *flat):

@@ -19,17 +19,25 @@ Protocol.
     `torch.autograd.grad(outputs that get gradients, differentiable inputs + parameters)` into a second graph, both in one memory pool;
   * afterwards a call = copy the inputs into the static buffers + replay; an autograd node (`_Replay`) hands the static outputs to
     the caller, and in the backward pass copies the incoming gradients, replays the backward graph, binds each parameter's static
-    gradient buffer as its `.grad` (accumulating out of place when one is already there - a `.grad` that is the static buffer itself is
-    copied out before the replay overwrites it -, running the parameter's post-accumulate hooks as AccumulateGrad would) and returns
-    the static input gradients.
+    gradient buffer as its `.grad` (accumulating out of place when one is already there), running the parameter's post-accumulate hooks
+    as AccumulateGrad would, and returns the static input gradients.
   * a replay is refused - the capture dropped, the eager path taken and a new warm-up started - when a parameter's version counter,
     storage or `requires_grad` changed since the capture (load_state_dict, manual surgery: the packed images the graph reads would be
     stale), when the gradient pattern differs, or under the per-launch profiling pass of bench.py.
-Outputs are views of static buffers: they are valid until the segment's next call (a training step consumes them at once).
+  * at most MAX_CAPTURES signatures per segment; the least recently used capture goes first.
+Memory.  Every capture of a segment is recorded into the segment's one pool, so a block that holds a static buffer of one capture (an
+activation its backward reads, a gradient bound as `.grad`) may be a temporary of another capture's graphs.  Hence:
+  * `.grad` tensors bound by any backward replay of the segment - evicted captures included - are listed on the segment and moved to private
+    copies before ANY forward or backward replay of the segment, unless the optimizer declared them read (`grads_consumed`, the training
+    step: no copy there);
+  * while a grad-mode replay's backward is still pending (two forwards before one backward: `f(x1) + f(x2)`), a further call of the segment
+    runs eagerly - same kernels, same bits - instead of replaying over the activations that backward will read.
+Outputs are views of static buffers: they are valid until the segment's next call, of any signature (a training step consumes them at once).
 """
 import os
 import threading
 import time
+import weakref
 
 import torch
 
@@ -86,8 +94,7 @@ def _copy_all(dst, src):
 
 
 class _Capture:
-    __slots__ = ("fwd", "bwd", "bwd2", "keep", "s_in", "s_out", "g_idx", "s_gout", "s_gin", "s_gparams", "diff_idx", "params", "pstate", "pool", "stream",
-                 "bound")
+    __slots__ = ("fwd", "bwd", "bwd2", "keep", "s_in", "s_out", "g_idx", "s_gout", "s_gin", "s_gparams", "diff_idx", "params", "pstate", "pool", "stream")
 
 
 class _Replay(torch.autograd.Function):
@@ -97,6 +104,7 @@ class _Replay(torch.autograd.Function):
     @staticmethod
     def forward(ctx, seg, cap, anchor, *diff_inputs):
         ctx.seg, ctx.cap = seg, cap
+        seg._pending = weakref.ref(ctx)   # cleared by this node's backward; dead when the caller drops the outputs without one
         t0 = time.perf_counter()
         cap.fwd.replay()
         stats["launch_host_ms"] += (time.perf_counter() - t0) * 1e3
@@ -108,6 +116,8 @@ class _Replay(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gouts):
         cap, seg = ctx.cap, ctx.seg
+        if seg._pending is not None and seg._pending() is ctx:
+            seg._pending = None
         dst, src = [], []
         for k, i in enumerate(cap.g_idx):
             g = gouts[i]
@@ -123,19 +133,15 @@ class _Replay(torch.autograd.Function):
                 # an output that received no gradient during the warm-up now has one: this capture cannot deliver it
                 raise RuntimeError(f"GraphedSegment '{seg.name}': output {i} received a gradient that the captured backward does not cover; "
                                    "call .reset() after changing which losses are used")
-        # Gradient accumulation (a second backward before the gradients were cleared, zero_grad(set_to_none=False)): a `.grad` that IS one of
-        # this capture's static buffers - bound by the previous backward - is about to be overwritten by the replay: its values move to a
-        # private copy first (enqueued ahead of both replays), and the sums below wait for the weight-gradient graph's stream.  ADVICE r05.
-        accumulate = False
-        for p, g in zip(cap.params, cap.s_gparams):
-            if g is not None and p.grad is not None:
-                accumulate = True
-                if p.grad.data_ptr() == g.data_ptr():
-                    p.grad = p.grad.clone()
+        # Gradient accumulation (a second backward before the gradients were cleared, zero_grad(set_to_none=False)): a `.grad` that IS a static
+        # buffer of this segment - bound by an earlier backward of any of its captures - may be overwritten by the replay: its values move to
+        # a private copy first, and the sums below wait for the weight-gradient graph's stream.  ADVICE r05 / r06.
+        dev = cap.s_in[0].device.index
+        seg._park(dev)
+        accumulate = any(g is not None and p.grad is not None for p, g in zip(cap.params, cap.s_gparams))
         t0 = time.perf_counter()
         cap.bwd.replay()
         stats["launch_host_ms"] += (time.perf_counter() - t0) * 1e3
-        dev = cap.s_in[0].device.index
         joined = cap.bwd2 is None
         if cap.bwd2 is not None:   # the weight gradients' graph: on the side stream, beside whatever the caller's backward does next
             from . import side
@@ -143,12 +149,12 @@ class _Replay(torch.autograd.Function):
             if accumulate:
                 side.join(dev)
                 joined = True
-        cap.bound = True   # static buffers are (about to be) somebody's .grad: see GraphedSegment.__call__
         for p, g in zip(cap.params, cap.s_gparams):
             if g is None:
                 continue
             if p.grad is None:
                 p.grad = g
+                seg._bound.append((p, g))   # (moved out of the pool before the segment's next replay: GraphedSegment._park)
             else:
                 p.grad = p.grad + g      # (never in place: p.grad may be another segment's static buffer)
             hooks = getattr(p, "_post_accumulate_grad_hooks", None)
@@ -166,18 +172,22 @@ class _Replay(torch.autograd.Function):
 _SEGMENTS = None   # weak set of live segments (grads_consumed)
 
 
-def grads_consumed():
-    """Called by a training step AFTER its optimizer has read the gradients (train_step.backward_and_step): the `.grad` tensors that are static
-    buffers of a capture need not survive the next forward replay - the step clears every `.grad` before its next backward anyway.  Without this
-    declaration the next forward replay first moves each of them to a private copy (gradient accumulation must not read a buffer the
-    forward graph reuses) - 164 clones per step for the S2D student (0.64 ms of copy kernels and ~1.6 ms of launch-thread time, r06 profile of the
-    graphed mode: `__amd_rocclr_copyBuffer` 180 launches per step against 16 in r05).  Reading such a `.grad` after the NEXT forward is then
-    undefined; code that accumulates over micro-batches simply does not call this."""
+def grads_consumed(params):
+    """Called by a training step AFTER its optimizer has read the gradients of `params` (train_step.backward_and_step): the `.grad` tensors of
+    those parameters that are static buffers of a capture need not survive the segment's next replay - the step clears every `.grad` before
+    its next backward anyway.  Without this declaration the next replay first moves each of them to a private copy (gradient
+    accumulation must not read a buffer the graphs reuse) - 164 clones per step for the S2D student (0.64 ms of copy kernels and ~1.6 ms of
+    launch-thread time, r06 profile of the graphed mode: `__amd_rocclr_copyBuffer` 180 launches per step against 16 in r05).  Reading such a
+    `.grad` after the segment's NEXT call is then undefined; code that accumulates over micro-batches simply does not call this.  Parameters
+    that were not stepped (another model's segment, accumulating across this step) keep their protection."""
     if _SEGMENTS is None:
         return
+    ids = None
     for seg in list(_SEGMENTS):
-        for cap in seg._caps.values():
-            cap.bound = False
+        if seg._bound:
+            if ids is None:
+                ids = {id(p) for p in params}
+            seg._bound = [(p, g) for p, g in seg._bound if id(p) not in ids]
 
 
 class GraphedSegment:
@@ -190,6 +200,8 @@ class GraphedSegment:
         self.params = [p for m in self.modules for p in m.parameters()]
         self._caps = {}       # signature -> _Capture
         self._seen = {}       # signature -> [calls so far, set of output indices that received a gradient]
+        self._bound = []      # (parameter, static gradient buffer) pairs a backward replay of any capture bound as `.grad`
+        self._pending = None  # weak reference to the autograd node of the grad-mode replay whose backward has not run yet
         self.pool = None
         global _SEGMENTS
         if _SEGMENTS is None:
@@ -200,6 +212,26 @@ class GraphedSegment:
     def reset(self):
         self._caps.clear()
         self._seen.clear()
+
+    def backward_pending(self):
+        """True while the outputs of a grad-mode replay are alive and their backward has not run: the segment's next call runs eagerly
+        (and a caller must not refill a persistent input buffer that backward reads)"""
+        node = None if self._pending is None else self._pending()
+        if node is None:
+            self._pending = None
+        return node is not None
+
+    def _park(self, dev):
+        """every `.grad` that is still one of the segment's static gradient buffers -> a private copy, ordered behind the weight-gradient
+        graph that may still be writing it on the side stream"""
+        moved = [p for p, g in self._bound if p.grad is not None and p.grad.data_ptr() == g.data_ptr()]
+        self._bound = []
+        if moved:
+            from . import side
+            side.join(dev)
+            for p in moved:
+                p.grad = p.grad.clone()
+            stats["parked"] += len(moved)
 
     # ------------------------------------------------------------------------------------------------------------------
     def _pstate(self):
@@ -230,6 +262,8 @@ class GraphedSegment:
                 del self._caps[key]
                 self._seen.pop(key, None)
                 stats["dropped"] += 1
+            else:
+                self._caps[key] = self._caps.pop(key)   # most recently used last: eviction takes the first
         if cap is None:
             seen = self._seen.setdefault(key, [0, set()])
             if seen[0] < WARMUP:
@@ -241,9 +275,11 @@ class GraphedSegment:
                         if torch.is_tensor(o) and o.requires_grad:
                             o.register_hook(lambda g, i=i, s=seen[1]: s.add(i))
                 return outs
-            if self.__dict__.get("_broken"):
-                stats["eager"] += 1
-                return self.fn(*inputs)
+        if self.backward_pending() or (cap is None and self.__dict__.get("_broken")):
+            # (pending: a capture or replay would write blocks of the pool - that capture's activations among them - before its backward reads them)
+            stats["eager"] += 1
+            return self.fn(*inputs)
+        if cap is None:
             try:
                 cap = self._capture(inputs, sorted(seen[1]), grad_mode)
             except Exception as e:   # something inside the segment cannot be recorded (a library call that allocates / synchronises): keep the
@@ -256,22 +292,18 @@ class GraphedSegment:
                 return self.fn(*inputs)
             self._caps[key] = cap
             while len(self._caps) > MAX_CAPTURES:   # signatures that can no longer occur (a padded side input grew its capacity) would only
-                old_key = next(iter(self._caps))    # hold graph-pool memory: the oldest capture goes
+                old_key = next(iter(self._caps))    # hold graph-pool memory: the least recently used capture goes
                 del self._caps[old_key]
                 self._seen.pop(old_key, None)
                 stats["dropped"] += 1
             stats["capture"] += 1
         stats["replay"] += 1
-        if getattr(cap, "bound", False):
-            # The previous backward bound static gradient buffers as `.grad`.  A training step clears them before the next forward; when it
-            # did not (gradient accumulation over micro-batches, zero_grad(set_to_none=False)) the values must leave the graph's memory pool
-            # BEFORE this forward replays: forward and backward graph share the pool, a block that holds a gradient in the backward graph
-            # may be a temporary of the forward graph (r06: a second backward accumulated onto garbage - tests/test_graph_gpu.py).
-            for p, g in zip(cap.params, cap.s_gparams):
-                if g is not None and p.grad is not None and p.grad.data_ptr() == g.data_ptr():
-                    p.grad = p.grad.clone()
-                    stats["parked"] += 1   # (a training step that called grads_consumed() never gets here)
-            cap.bound = False
+        if self._bound:
+            # The last backward bound static gradient buffers as `.grad`.  A training step clears them before the next forward; when it did not
+            # (gradient accumulation over micro-batches, zero_grad(set_to_none=False)) the values must leave the graph pool BEFORE this forward
+            # replays: a block that holds a gradient of one graph may be a temporary of this one (r06: a second backward accumulated onto
+            # garbage - tests/test_graph_gpu.py).  (A training step that called grads_consumed() parks nothing here.)
+            self._park(cap.s_in[0].device.index)
         with torch.no_grad():   # ONE multi-tensor copy kernel for all inputs (a hipMemcpyAsync per tensor costs the host ~60 us each under load)
             pairs = [(s, t) for s, t in zip(cap.s_in, inputs) if s.data_ptr() != t.data_ptr()]
             if pairs:
@@ -295,7 +327,7 @@ class GraphedSegment:
         from . import side
         key = (tuple(_sig(t) for t in inputs), torch.is_grad_enabled(), torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype(), frozenset(side.GRAPH_KINDS), frozenset(side.GRAPH_DEFER))
         cap = self._caps.get(key)
-        return None if cap is None else cap.s_in[index]
+        return None if cap is None or self.backward_pending() else cap.s_in[index]
 
     # ------------------------------------------------------------------------------------------------------------------
     def _capture(self, inputs, g_idx, grad_mode):
@@ -400,7 +432,6 @@ class GraphedSegment:
                                 cap.s_gparams[slot[id(prm)]] = g
                     cap.keep = items
             cap.s_out = tuple(o.detach() if torch.is_tensor(o) else o for o in outs)
-            cap.bound = False
         finally:
             if gc_was_on:
                 gc.enable()

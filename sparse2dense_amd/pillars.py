@@ -604,7 +604,7 @@ class KD_PointPillars(PointPillars):
             coors, feat = self._recon_list(example)
             if self._graph_ok(canvas):
                 tasks = len(self.bbox_head.tasks)
-                cb, fb = self._padded_list("pillar", coors, feat)
+                cb, fb = self._padded_list("pillar", coors, feat, self._segments_busy())
                 self._flush_recon()
                 return self._run_segment("train:pillar", lambda c_, cb_, fb_, *flat: self._dense_part(c_, self._unflat_targets(flat, tasks), cb_, fb_),
                                          canvas, [cb, fb] + self._flat_targets(example, tasks), modules=[self.backbone, self.neck, self.bbox_head])

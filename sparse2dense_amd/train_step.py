@@ -79,10 +79,11 @@ def backward_and_step(loss, params, optimizer, scheduler=None, iteration=None, m
     """One OptimizerHook.after_train_iter of the reference (hooks/optimizer.py:15-21) with its optimizer (apis/train.py:168-186,
     fastai OptimWrapper Adam + true weight decay under the OneCycle schedule): schedule step -> zero_grad -> backward (+ overlapped
     gradient all-reduce) -> clip(35) and update in the fused multi-tensor kernels (solver.OneCycleAdam.clip_and_step)."""
+    params = list(params)
     if scheduler is not None:
         scheduler.step(iteration)
     backward_and_clip(loss, params, None)
     norm = optimizer.clip_and_step(max_norm)
     from . import graphed
-    graphed.grads_consumed()   # (the next call clears every .grad before its backward: a graphed segment need not park them over its next forward)
+    graphed.grads_consumed(params)   # (the next call clears these .grad before its backward: a graphed segment need not park them over its next replay)
     return norm
