@@ -796,6 +796,51 @@ int s2d_assign_label(const float *gt_boxes, const int32_t *gt_classes, int frame
                      float *gt_boxes_and_cls, s2d_stream_t stream);
 
 /*
+ * SECOND anchor head (csrc/anchor_head.hip), Waymo configuration: ground_box3d_coder 7-wide (x,y,z,w,l,h,r), nearest-IoU similarity, no
+ * sampling, no anchors_mask.  anchors: fp32 [num_anchors][7], shared by the frames; anchor a sits in slot a % (num_classes * rotations) of
+ * its cell and slots [c * rotations, (c + 1) * rotations) belong to class c (det3d/core/anchor/target_assigner.py:139-158).
+ *
+ * s2d_anchor_assign = AssignTarget.__call__ in train mode (det3d/datasets/pipelines/preprocess.py:726-830: per-class split,
+ * limit_period(yaw, 0.5, 2 pi)) over TargetAssigner.assign_v2 (target_assigner.py:68-137) and create_target_np
+ * (det3d/core/anchor/target_ops.py:29-223) with rbbox2d_to_near_bbox / iou_jit(eps = 0) / second_box_encode
+ * (det3d/core/bbox/box_np_ops.py:131-143,497-535,1002-1063).  gt_boxes fp32 [frames][max_boxes][7], gt_classes int32 [frames][max_boxes]
+ * (1-based; <= 0 = padding; max_boxes <= 500); matched / unmatched thresholds: HOST arrays of num_classes floats.  Outputs: labels int32
+ * [frames][num_anchors] (-1 ignore, 0 negative, class id positive), reg_targets fp32 [frames][num_anchors][7], reg_weights fp32
+ * [frames][num_anchors].  Overlaps are computed with float64 intermediates and rounded once to fp32, as the numba loop does.
+ */
+size_t s2d_anchor_assign_workspace_bytes(int frames, int max_boxes);
+int s2d_anchor_assign(const float *gt_boxes, const int32_t *gt_classes, int frames, int max_boxes, const float *anchors,
+                      int64_t num_anchors, int num_classes, int rotations, const float *matched_thresholds,
+                      const float *unmatched_thresholds, int32_t *labels, float *reg_targets, float *reg_weights, void *ws,
+                      size_t ws_bytes, s2d_stream_t stream);
+/*
+ * MultiGroupHead.loss for one task (det3d/models/bbox_heads/mg_head.py:535-667 with prepare_loss_weights NormByNumPositives, create_loss,
+ * add_sin_difference, get_direction_target, _get_pos_neg_loss of mg_head.py:29-63,147-188 and SigmoidFocalLoss / WeightedSmoothL1Loss
+ * (codewise) / WeightedSoftmaxClassificationLoss of det3d/models/losses/losses.py:147-222,293-359,431-469).  box_preds fp32
+ * [frames][num_anchors][7], cls_preds [frames][num_anchors][num_classes], dir_cls_preds [frames][num_anchors][2] (the NHWC head outputs).
+ * params: HOST array of 9 floats - pos_cls_weight, neg_cls_weight, focal alpha, focal gamma (must be 2), smooth-L1 sigma, loss weights of
+ * loc / cls / dir, direction_offset.  res (device, 15 floats): loss, cls_pos_loss, cls_neg_loss, dir_loss_reduced, cls_loss_reduced,
+ * loc_loss_reduced, loc_loss_elem[7], num_pos and num_neg of frame 0.  norm (device, frames floats): 1 / clamp(positives of the frame, 1),
+ * read by the backward.  _bwd: d_* = grad_loss[0] (device scalar) * d loss / d preds, every element written.
+ */
+size_t s2d_anchor_loss_workspace_bytes(int frames);
+int s2d_anchor_loss_fwd(const float *box_preds, const float *cls_preds, const float *dir_cls_preds, const int32_t *labels,
+                        const float *reg_targets, const float *anchors, int frames, int64_t num_anchors, int num_classes,
+                        const float *params, float *res, float *norm, void *ws, size_t ws_bytes, s2d_stream_t stream);
+int s2d_anchor_loss_bwd(const float *box_preds, const float *cls_preds, const float *dir_cls_preds, const int32_t *labels,
+                        const float *reg_targets, const float *anchors, int frames, int64_t num_anchors, int num_classes,
+                        const float *params, const float *norm, const float *grad_loss, float *d_box_preds, float *d_cls_preds,
+                        float *d_dir_cls_preds, s2d_stream_t stream);
+/*
+ * The per-anchor part of MultiGroupHead.predict (mg_head.py:737-765,838-849,995-1001): second_box_decode
+ * (det3d/core/bbox/box_torch_ops.py:87-150) -> boxes fp32 [frames][num_anchors][7]; scores = max sigmoid(cls) and its class -> labels
+ * int32; dir_labels = argmax(dir_cls_preds) (0 when dir_cls_preds is null); keep uint8 = scores >= score_threshold.
+ */
+int s2d_anchor_decode(const float *box_preds, const float *cls_preds, const float *dir_cls_preds, const float *anchors, int frames,
+                      int64_t num_anchors, int num_classes, float score_threshold, float *boxes, float *scores, int32_t *labels,
+                      int32_t *dir_labels, uint8_t *keep, s2d_stream_t stream);
+
+/*
  * Optimizer step of the reference's training loop (det3d/torchie/apis/train.py:168-186, det3d/solver/fastai_optim.py:158-171,
  * hooks/optimizer.py:15-21): gradient L2 norm -> clip coefficient (device scalar, clip_grad_norm_ semantics) -> fused
  * multi-tensor Adam with decoupled weight decay: p *= 1 - lr*wd; Adam(betas, eps) on grad*clip_coef with bias correction of

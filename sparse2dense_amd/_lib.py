@@ -367,6 +367,18 @@ SIGNATURES = {
                                            ctypes.c_void_p]),
     "s2d_densify_bwd_f32": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int64, ctypes.c_int, _I3, ctypes.c_int, c_f32p,
                                            ctypes.c_void_p]),
+    # SECOND anchor head (csrc/anchor_head.hip); thresholds / params are HOST float arrays
+    "s2d_anchor_assign_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "s2d_anchor_assign": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_i32p, c_f32p, c_f32p, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_anchor_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "s2d_anchor_loss_fwd": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_float), c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_anchor_loss_bwd": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "s2d_anchor_decode": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_float, c_f32p,
+                                         c_f32p, c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _lib = None

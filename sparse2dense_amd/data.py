@@ -29,9 +29,12 @@ class SyntheticFrames:
     """Holds B seeded scenes on the device (points + targets); `example()` runs the device
     voxelizer and returns the collated dict — i.e. the per-iteration data work of the hot path."""
 
-    def __init__(self, batch_size, n_points=150000, seed=20240928, distill=False, device="cuda", beam_jitter=2e-4):
+    def __init__(self, batch_size, n_points=150000, seed=20240928, distill=False, device="cuda", beam_jitter=2e-4, anchor_targets=None):
         self.device = torch.device(device)
         self.distill = distill
+        # opt-in: the `assigner` dictionary of a SECOND config (waymo_configs.SECOND_ASSIGNER) - example() then also carries the anchor
+        # head's targets (anchors / labels / reg_targets / reg_weights, anchors.assign_anchor_targets; device only)
+        self.anchor_targets = anchor_targets
         self.gens = waymo_generators(distill)
         self.points, self.dense_points, self.recon_points = [], [], []
         gt_b, gt_c = [], []
@@ -90,6 +93,12 @@ class SyntheticFrames:
                         ex[k + suf] = v
         ex["shape"] = np.stack([self.grid_size] * len(self.points))
         ex.update(self._targets())
+        if self.anchor_targets is not None:
+            from . import anchors as _anchors
+            if self.device.type != "cuda":
+                raise _anchors._lib.S2DError("SyntheticFrames(anchor_targets=...) needs a CUDA device (no CPU fallback)")
+            ex.update(_anchors.assign_anchor_targets(self.gt_boxes, self.gt_classes, self.anchor_targets,
+                                                     grid_xy=(int(self.grid_size[0]), int(self.grid_size[1]))))
         return ex
 
 

@@ -229,7 +229,8 @@ class VoxelNet(SingleStageDetector):
         return neck, preds, losses
 
     def _dense_call(self, x, example, return_loss):
-        if self._graph_ok(x) and self.with_neck:
+        # (an anchor head's loss reads labels / reg_targets / anchors, which `_flat_targets` does not carry: its dense segment stays eager)
+        if self._graph_ok(x) and self.with_neck and getattr(self.bbox_head, "graph_segment", True):
             tasks = len(self.bbox_head.tasks)
             name = f"{'train' if self.training else 'eval'}:{'loss' if return_loss else 'fwd'}:{int(torch.is_grad_enabled())}"
             if return_loss:
@@ -259,7 +260,7 @@ class VoxelNet(SingleStageDetector):
             return losses if not return_feature else (losses, F_D_a, F_D_b)
         if return_feature and return_recon_feature:
             return preds, F_D_a, F_D_b
-        if kwargs.get("raw_preds", False):   # forward-only use (SECOND config 1: anchor decode is out of scope)
+        if kwargs.get("raw_preds", False):   # the raw head maps (bench.py and the forward parity test of SECOND config 1 use them)
             return preds
         boxes = self.bbox_head.predict(example, preds, self.test_cfg)
         return boxes if not return_feature else (boxes, F_D_a, F_D_b)

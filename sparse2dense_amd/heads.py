@@ -835,7 +835,7 @@ class CenterHead(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------
-# SECOND anchor head — forward only (BASELINE config 1)
+# SECOND anchor head (BASELINE config 1)
 # ----------------------------------------------------------------------------------------------
 @HEADS.register_module
 class Head(nn.Module):
@@ -861,8 +861,12 @@ class Head(nn.Module):
 @HEADS.register_module
 class MultiGroupHead(nn.Module):
     """Constructor signature and parameter names of the reference head
-    (/root/reference/det3d/models/bbox_heads/mg_head.py:386-533); `forward` is on the hot path of
-    config 1, the anchor loss / target assignment / NMS are out of scope."""
+    (/root/reference/det3d/models/bbox_heads/mg_head.py:386-533).  `loss` and `predict` cover the Waymo SECOND configuration (3d mode,
+    ground_box3d_coder, NormByNumPositives, SigmoidFocalLoss, codewise WeightedSmoothL1Loss, softmax direction classifier, sin-difference
+    angle coding, rotated single-class NMS) through the kernels of csrc/anchor_head.hip (sparse2dense_amd/anchors.py); any other
+    combination raises NotImplementedError naming the option."""
+
+    graph_segment = False   # detectors._dense_call: neck + this head (+ loss) are not replayed as HIP graphs (eager launches)
 
     def __init__(self, mode="3d", in_channels=[128, ], norm_cfg=None, tasks=[], weights=[], num_classes=[1, ],
                  box_coder=None, with_cls=True, with_reg=True, reg_class_agnostic=False, encode_background_as_zeros=True,
@@ -870,18 +874,26 @@ class MultiGroupHead(nn.Module):
                  loss_aux=None, direction_offset=0.0, name="rpn", logger=None):
         super().__init__()
         assert with_cls or with_reg
+        from . import anchors as _anchors
         num_classes = [len(t["class_names"]) for t in tasks]
         self.class_names = [t["class_names"] for t in tasks]
         self.num_anchor_per_locs = [2 * n for n in num_classes]
-        self.box_coder = box_coder
+        # a coder object, or the dictionary the shim's det3d.builder.build_box_coder returns
+        try:
+            self.box_coder = _anchors.build_box_coder(box_coder)
+        except NotImplementedError:   # the head still builds and runs forward; loss / predict name the option
+            self.box_coder = box_coder
         code_size = box_coder["code_size"] if isinstance(box_coder, dict) else box_coder.code_size
         self.in_channels = in_channels
         self.num_classes = num_classes
         self.encode_background_as_zeros = encode_background_as_zeros
         self.use_sigmoid_score = use_sigmoid_score
         self.box_n_dim = code_size
+        self.anchor_dim = code_size
         self.use_direction_classifier = loss_aux is not None
         self.direction_offset = direction_offset
+        self.encode_rad_error_by_sin = encode_rad_error_by_sin
+        self.loss_norm, self.loss_cls, self.loss_reg, self.loss_aux = loss_norm, loss_cls, loss_bbox, loss_aux
         self.bev_only = mode == "bev"
         self.tasks = nn.ModuleList()
         for num_c, num_a in zip(num_classes, self.num_anchor_per_locs):
@@ -893,8 +905,97 @@ class MultiGroupHead(nn.Module):
     def forward(self, x):
         return [task(x) for task in self.tasks]
 
-    def loss(self, example, preds_dicts, **kwargs):
-        raise NotImplementedError("MultiGroupHead.loss (anchor targets / box coders) is out of scope of the hot path")
+    def _check_supported(self, what, example, kwargs):
+        from . import anchors as _anchors
+        if self.bev_only:
+            raise NotImplementedError(f"MultiGroupHead.{what}: mode='bev' is not supported")
+        if not self.encode_background_as_zeros:
+            raise NotImplementedError(f"MultiGroupHead.{what}: encode_background_as_zeros=False is not supported")
+        if not self.use_sigmoid_score:
+            raise NotImplementedError(f"MultiGroupHead.{what}: use_sigmoid_score=False is not supported")
+        if not isinstance(self.box_coder, _anchors.GroundBox3dCoder):
+            raise NotImplementedError(f"MultiGroupHead.{what}: box coder {self.box_coder!r} is not supported (ground_box3d_coder with n_dim=7, "
+                                      "linear_dim=False, encode_angle_vector=False only)")
+        if kwargs.get("mode", False):
+            raise NotImplementedError(f"MultiGroupHead.{what}: the 'mode' keyword (bev regression subset) is not supported")
+        if "anchors_mask" in example:
+            raise NotImplementedError(f"MultiGroupHead.{what}: anchors_mask (pos_area_threshold >= 0) is not supported")
+        if "anchors" not in example:
+            from ._lib import S2DError
+            raise S2DError(f"MultiGroupHead.{what}: the example carries no 'anchors' (anchors.assign_anchor_targets produces them)")
 
+    @staticmethod
+    def _task_anchors(example, task_id):
+        a = example["anchors"][task_id]
+        return a[0] if a.dim() == 3 else a   # the same table for every frame
+
+    def loss(self, example, preds_dicts, **kwargs):
+        """mg_head.py:580-695 - one fused pass + finalize per task (anchors.AnchorLossFn).  The logging values the reference moves to the
+        host stay device scalars; `loss` carries the graph."""
+        from . import anchors as _anchors
+        self._check_supported("loss", example, kwargs)
+        params = self.__dict__.get("_loss_params")
+        if params is None:
+            params = self.__dict__["_loss_params"] = _anchors.loss_params(self.loss_norm, self.loss_cls, self.loss_reg, self.loss_aux,
+                                                                           self.direction_offset, self.encode_rad_error_by_sin)
+        merged = defaultdict(list)
+        for task_id, preds in enumerate(preds_dicts):
+            ret = _anchors.anchor_loss(preds["box_preds"], preds["cls_preds"], preds["dir_cls_preds"], example["labels"][task_id],
+                                       example["reg_targets"][task_id], self._task_anchors(example, task_id), params)
+            for k, v in ret.items():
+                merged[k].append(v)
+        return merged
+
+    @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):
-        raise NotImplementedError("MultiGroupHead.predict (anchor decode + NMS) is out of scope of the hot path")
+        """mg_head.py:697-1086, single-class-NMS branch: decode + score threshold in one kernel (anchors.decode_anchors), candidates in
+        anchor order, top nms_pre_max_size by score, rotated NMS on the device, nms_post_max_size, direction flip, centre-range mask.
+        The reference feeds rotate_nms_cc with (x, y, w, l, r) rectangles that turn clockwise for positive r (box_np_ops.py:207-220);
+        the same rectangle in the (x, y, z, dx, dy, dz, heading) form of nms.rotate_nms is (dx, dy, heading) = (w, l, -r)."""
+        import math
+        from . import anchors as _anchors
+        from .nms import rotate_nms
+        self._check_supported("predict", example, kwargs)
+        get = (lambda k, d=None: test_cfg.get(k, d)) if hasattr(test_cfg, "get") else (lambda k, d=None: getattr(test_cfg, k, d))
+        nms_cfg = get("nms")
+        nget = (lambda k, d=None: nms_cfg.get(k, d)) if isinstance(nms_cfg, dict) else (lambda k, d=None: getattr(nms_cfg, k, d))
+        if not nget("use_rotate_nms", False):
+            raise NotImplementedError("MultiGroupHead.predict: test_cfg.nms.use_rotate_nms=False is not supported")
+        if nget("use_multi_class_nms", False):
+            raise NotImplementedError("MultiGroupHead.predict: test_cfg.nms.use_multi_class_nms=True is not supported")
+        score_threshold = float(get("score_threshold"))
+        if not score_threshold > 0.0:
+            raise NotImplementedError("MultiGroupHead.predict: test_cfg.score_threshold <= 0 is not supported")
+        pcr = get("post_center_limit_range")
+        rets = []
+        for task_id, preds in enumerate(preds_dicts):
+            boxes, scores, labels, dirs, keep = _anchors.decode_anchors(preds["box_preds"], preds["cls_preds"],
+                                                                        preds.get("dir_cls_preds") if self.use_direction_classifier else None,
+                                                                        self._task_anchors(example, task_id), score_threshold)
+            pcr_t = torch.tensor(pcr, dtype=torch.float32, device=boxes.device) if pcr is not None and len(pcr) > 0 else None
+            task = []
+            for i in range(boxes.shape[0]):
+                k = keep[i]
+                b, s, l, d = boxes[i][k], scores[i][k], labels[i][k].long(), dirs[i][k]
+                if b.shape[0]:
+                    nms_boxes = torch.cat((b[:, :6], -b[:, 6:7]), 1)
+                    sel = rotate_nms(nms_boxes, s, nget("nms_iou_threshold"), nget("nms_pre_max_size"), nget("nms_post_max_size"))
+                    b, s, l, d = b[sel], s[sel], l[sel], d[sel]
+                if b.shape[0] and self.use_direction_classifier:
+                    opp = ((b[:, 6] - self.direction_offset) > 0) ^ d.bool()
+                    b[:, 6] += torch.where(opp, b.new_tensor(math.pi), b.new_tensor(0.0))
+                if b.shape[0] and pcr_t is not None:
+                    m = (b[:, :3] >= pcr_t[:3]).all(1) & (b[:, :3] <= pcr_t[3:]).all(1)
+                    b, s, l = b[m], s[m], l[m]
+                task.append(dict(box3d_lidar=b, scores=s, label_preds=l))
+            rets.append(task)
+        meta = example.get("metadata") if isinstance(example, dict) else None
+        out = []
+        for i in range(len(rets[0])):
+            flag, labels = 0, []
+            for j, num_class in enumerate(self.num_classes):   # label offsets of the later tasks (mg_head.py:794-799)
+                labels.append(rets[j][i]["label_preds"] + flag)
+                flag += num_class
+            out.append(dict(box3d_lidar=torch.cat([r[i]["box3d_lidar"] for r in rets]), scores=torch.cat([r[i]["scores"] for r in rets]),
+                            label_preds=torch.cat(labels), metadata=meta[i] if meta else None))
+        return out

@@ -6,6 +6,7 @@ det3d_shim.Config.fromfile; these literals exist so that bench.py and the GPU te
   centerpoint_voxelnet()   configs/waymo/voxelnet/waymo_centerpoint_voxelnet_3x_distill_interval_5.py:18-46  (`model`, teacher / plain)
   s2d_student()            same file :48-76 (`S_model`)
   second_voxelnet_parts()  configs/waymo/voxelnet/waymo_second_3x_interval_5.py (reader/backbone/neck of config 1)
+  second_voxelnet_train()  same file :58-106 with the full head dictionaries (:78-105); SECOND_ASSIGNER :15-55,108-113; SECOND_TEST_CFG :117-130
 """
 import logging
 
@@ -49,6 +50,47 @@ def second_voxelnet():
                                encode_background_as_zeros=True, use_sigmoid_score=True, encode_rad_error_by_sin=True,
                                loss_aux=dict(type="WeightedSoftmaxClassificationLoss", name="direction_classifier",
                                              loss_weight=0.2), direction_offset=0.0))
+
+
+SECOND_BOX_CODER = dict(type="ground_box3d_coder", n_dim=7, linear_dim=False, encode_angle_vector=False)
+
+
+def _anchor_generator(sizes, matched, unmatched, class_name):
+    return dict(type="anchor_generator_range", sizes=sizes, anchor_ranges=[-74.88, -74.88, 0, 74.88, 74.88, 0], rotations=[0, 1.57],
+                matched_threshold=matched, unmatched_threshold=unmatched, class_name=class_name)
+
+
+# `assigner` of the config (train_cfg.assigner): what anchors.assign_anchor_targets takes
+SECOND_ASSIGNER = dict(
+    box_coder=SECOND_BOX_CODER,
+    target_assigner=dict(type="iou",
+                         anchor_generators=[_anchor_generator([2.08, 4.73, 1.77], 0.55, 0.4, "VEHICLE"),
+                                            _anchor_generator([0.84, 0.91, 1.74], 0.5, 0.35, "PEDESTRIAN"),
+                                            _anchor_generator([0.84, 1.81, 1.77], 0.5, 0.3, "CYCLIST")],
+                         sample_positive_fraction=-1, sample_size=512,
+                         region_similarity_calculator=dict(type="nearest_iou_similarity"), pos_area_threshold=-1, tasks=TASKS),
+    out_size_factor=8, debug=False)
+
+SECOND_TEST_CFG = dict(post_center_limit_range=[-80, -80, -10.0, 80, 80, 10.0], max_per_img=4096,
+                       nms=dict(use_rotate_nms=True, use_multi_class_nms=False, nms_pre_max_size=1000, nms_post_max_size=100,
+                                nms_iou_threshold=0.01),
+                       score_threshold=0.1, pc_range=[-74.88, -74.88], out_size_factor=8)
+
+
+def second_voxelnet_train():
+    """configs/waymo/voxelnet/waymo_second_3x_interval_5.py:58-106 with every head dictionary: the model that trains and tests"""
+    parts = second_voxelnet_parts()
+    return dict(type="VoxelNet", pretrained=None, **parts,
+                bbox_head=dict(type="MultiGroupHead", mode="3d", in_channels=sum([128, ]), tasks=TASKS, weights=[1, ],
+                               box_coder=dict(SECOND_BOX_CODER, code_size=7), encode_background_as_zeros=True,
+                               loss_norm=dict(type="NormByNumPositives", pos_cls_weight=1.0, neg_cls_weight=2.0),
+                               loss_cls=dict(type="SigmoidFocalLoss", alpha=0.25, gamma=2.0, loss_weight=1.0),
+                               use_sigmoid_score=True,
+                               loss_bbox=dict(type="WeightedSmoothL1Loss", sigma=3.0, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0],
+                                              codewise=True, loss_weight=2.0),
+                               encode_rad_error_by_sin=True,
+                               loss_aux=dict(type="WeightedSoftmaxClassificationLoss", name="direction_classifier", loss_weight=0.2),
+                               direction_offset=0.0))
 
 
 def second_voxelnet_parts():
