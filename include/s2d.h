@@ -983,6 +983,36 @@ int s2d_pfn2_bwd_f32(const float *voxels, const int32_t *num_points, const int32
                      const float *scale_shift1, const float *abd2, const float *gout, const uint8_t *argmax, int64_t pillars, int slots,
                      int ndim, float vx, float vy, float x_offset, float y_offset, float *partial, s2d_stream_t stream);
 
+/*
+ * Deformable convolution v1 (csrc/deform_conv.hip), the kernels behind CenterHead(dcn_head=True)'s FeatureAdaption
+ * (det3d/models/bbox_heads/center_head.py:25-63).  Replaces det3d/ops/dcn: deform_conv_cuda.deform_conv_forward_cuda,
+ * deform_conv_backward_input_cuda and deform_conv_backward_parameters_cuda (deform_conv.py DeformConvFunction; the im2col / col2im /
+ * col2im_coord kernels of src/deform_conv_cuda_kernel.cu + GEMM).  No column buffer: the forward needs no workspace.
+ * x, y, dy, y_saved, dx: bf16 NHWC.  offset / d_offset: NHWC [n][ho][wo][dg*2*kh*kw] in the reference's channel order (channel
+ * g*2*kh*kw + 2*(i*kw+j) = row offset of tap (i, j), + 1 = column offset), fp32 (offset_bf16 = 0) or bf16 (1).  weight / dweight: fp32
+ * [cout][cin][kh][kw]; the two packed images hold kh*kw*cin*cout bf16 each.
+ * _supported: 1 for 64 -> 64, 3x3, stride 1, padding 1, dilation 1, groups 1, dg 4 - the shape the GPU suite runs the kernels at; 0
+ * otherwise (the caller's composite path).  relu: ReLU fused into the forward epilogue; the backward entries take the saved OUTPUT as y_saved and
+ * re-derive the mask from it (NULL: no ReLU).  _bwd_data: dx accumulates in the fp32 workspace (zeroed by a kernel, fp32 atomics), then
+ * is stored as bf16; d_offset has one owner per element (deterministic).  _wgrad: per-workgroup partials in the workspace, folded in
+ * a fixed order (deterministic).  Offsets may hold any value (NaN, Inf, +-1e6): positions outside the sampling window read and write
+ * nothing.
+ */
+int s2d_deform_conv_supported(int cin, int cout, int kh, int kw, int stride, int pad, int dil, int groups, int dg);
+size_t s2d_deform_conv_workspace_bytes(int n_img, int h, int w, int cin, int cout, int kh, int kw);
+int s2d_deform_conv_pack_weights_bf16(const float *weight, int cin, int cout, int kh, int kw, void *packed_fwd, void *packed_bwd,
+                                      s2d_stream_t stream);
+int s2d_deform_conv_nhwc_bf16(const void *x, const void *offset, int offset_bf16, const void *packed_fwd, int n_img, int h, int w, int cin,
+                              int cout, int kh, int kw, int stride, int pad, int dil, int dg, int relu, void *y, s2d_stream_t stream);
+size_t s2d_deform_conv_bwd_data_workspace_bytes(int n_img, int h, int w, int cin);
+int s2d_deform_conv_bwd_data_nhwc_bf16(const void *x, const void *offset, int offset_bf16, const void *dy, const void *y_saved,
+                                       const void *packed_bwd, int n_img, int h, int w, int cin, int cout, int kh, int kw, int stride,
+                                       int pad, int dil, int dg, void *dx, void *d_offset, void *ws, size_t ws_bytes, s2d_stream_t stream);
+size_t s2d_deform_conv_wgrad_workspace_bytes(int n_img, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int dil);
+int s2d_deform_conv_wgrad_nhwc_bf16(const void *x, const void *offset, int offset_bf16, const void *dy, const void *y_saved, int n_img,
+                                    int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int dil, int dg, float *dweight,
+                                    void *ws, size_t ws_bytes, s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -379,6 +379,19 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "s2d_anchor_decode": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_float, c_f32p,
                                          c_f32p, c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_void_p]),
+    # deformable convolution v1 (csrc/deform_conv.hip)
+    "s2d_deform_conv_supported": (ctypes.c_int, [ctypes.c_int] * 9),
+    "s2d_deform_conv_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),
+    "s2d_deform_conv_pack_weights_bf16": (ctypes.c_int, [c_f32p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3),
+    "s2d_deform_conv_nhwc_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 12 +
+                                  [ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_deform_conv_bwd_data_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "s2d_deform_conv_bwd_data_nhwc_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p] + [ctypes.c_int] * 11 +
+                                           [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_deform_conv_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
+    "s2d_deform_conv_wgrad_nhwc_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] +
+                                        [ctypes.c_int] * 11 + [c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -23,7 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # `v_pk_fma_f32` returned different high-lane sums while another queue's MFMA kernel shared the SIMDs (DESIGN rule 36), and the default
 # graphed mode does run weight-gradient MFMA kernels on a second queue.  Costs 0.1 ms per step.  S2D_BUILD_LOSSES_SLP=1 restores the
 # vectorised build for A/B runs.
-EXTRA = {}
+# deform_conv.hip is built the same way for the same reason: its fp32 bilinear blend (four products and three sums per channel) is a
+# packed-FP32 candidate, and its weight-gradient launch runs on the side stream beside the chain's MFMA kernels (rule 36).
+EXTRA = {"deform_conv.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("S2D_BUILD_LOSSES_SLP") != "1":
     EXTRA["losses.hip"] = ["-fno-slp-vectorize"]
 

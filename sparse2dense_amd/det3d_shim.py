@@ -10,6 +10,7 @@ and call sites load our implementation as a drop-in for the hot path:
 Provided module paths (everything else of det3d is out of scope and absent on purpose):
   det3d.models{,.registry,.builder}            registries + build_* (same keys)
   det3d.ops.point_cloud.point_cloud_ops        points_to_voxel
+  det3d.ops.dcn                                DeformConv, DeformConvFunction, deform_conv  (sparse2dense_amd/dcn.py; DCN v1 only)
   det3d.core.input.voxel_generator             VoxelGenerator
   det3d.utils.config_tool                      get_downsample_factor  (config_tool.py:39-53; imported by configs)
   det3d.builder                                build_box_coder stub   (imported by the SECOND configs)
@@ -120,7 +121,7 @@ def install():
         return
     if "det3d" in sys.modules and not getattr(sys.modules["det3d"], "__s2d_shim__", False):
         raise RuntimeError("a real det3d package is already imported; the shim would shadow it")
-    from . import backbones, detectors, heads, necks, pillars, registry, spconv, voxel_ops  # noqa: F401 (registers keys)
+    from . import backbones, dcn, detectors, heads, necks, pillars, registry, spconv, voxel_ops  # noqa: F401 (registers keys)
 
     _module("det3d", __s2d_shim__=True)
     reg_attrs = {k: getattr(registry, k) for k in ["READERS", "BACKBONES", "NECKS", "HEADS", "LOSSES", "DETECTORS",
@@ -139,6 +140,7 @@ def install():
     _module("det3d.ops")
     _module("det3d.ops.point_cloud")
     _module("det3d.ops.point_cloud.point_cloud_ops", points_to_voxel=voxel_ops.points_to_voxel)
+    _module("det3d.ops.dcn", DeformConv=dcn.DeformConv, DeformConvFunction=dcn.DeformConvFunction, deform_conv=dcn.deform_conv)
     _module("det3d.core")
     _module("det3d.core.input")
     _module("det3d.core.input.voxel_generator", VoxelGenerator=voxel_ops.VoxelGenerator)

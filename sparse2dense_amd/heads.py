@@ -1,6 +1,7 @@
 """CenterHead and its losses under the reference's registry keys.
 
   HEADS["CenterHead"], SepHead     /root/reference/det3d/models/bbox_heads/center_head.py:65-110,167-291
+  FeatureAdaption, DCNSepHead      det3d/models/bbox_heads/center_head.py:25-63,112-164 (dcn_head=True: the nuScenes DCN configs)
   FastFocalLoss, RegLoss           /root/reference/det3d/models/losses/centernet_loss.py:6-54
   _transpose_and_gather_feat       /root/reference/det3d/core/utils/center_utils.py:66-80
   distillation losses              /root/reference/det3d/torchie/trainer/trainer.py:38-76,783-805
@@ -18,6 +19,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .dcn import DeformConv
 from .dense2d import Conv3x3, FastBatchNorm2d, SmallConv3x3, fuse_bn_relu
 from .registry import HEADS, LOSSES
 
@@ -663,6 +665,51 @@ class SepHead(nn.Module):
         return {head: getattr(self, head)(x) for head in self.heads}
 
 
+class FeatureAdaption(nn.Module):
+    """conv_offset (1x1, bias, zero-initialised weight) -> ReLU(DeformConv(x, offset)) (center_head.py:25-63).  The ReLU runs in the
+    deformable conv's epilogue.  conv_offset has deformable_groups * 18 = 72 output channels, which none of the hand-written 1x1 kernels
+    takes; under bf16 autocast on channels_last features its output already is bf16 channels_last, which the deformable conv reads as is."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, deformable_groups=4):
+        super().__init__()
+        offset_channels = kernel_size * kernel_size * 2
+        self.conv_offset = nn.Conv2d(in_channels, deformable_groups * offset_channels, 1, bias=True)
+        self.conv_adaption = DeformConv(in_channels, out_channels, kernel_size=kernel_size, padding=(kernel_size - 1) // 2,
+                                        deformable_groups=deformable_groups)
+        self.conv_adaption.fused_relu = True
+        self.relu = nn.ReLU(inplace=True)   # (kept as an attribute like the reference's; applied by conv_adaption)
+        self.init_offset()
+
+    def init_offset(self):
+        self.conv_offset.weight.data.zero_()
+
+    def forward(self, x):
+        return self.conv_adaption(x, self.conv_offset(x))
+
+
+class DCNSepHead(nn.Module):
+    """center_head.py:112-164: separate deformable feature adaption for the heatmap and for the regression branches"""
+
+    def __init__(self, in_channels, num_cls, heads, head_conv=64, final_kernel=1, bn=False, init_bias=-2.19, **kwargs):
+        super().__init__(**kwargs)
+        self.feature_adapt_cls = FeatureAdaption(in_channels, in_channels, kernel_size=3, deformable_groups=4)
+        self.feature_adapt_reg = FeatureAdaption(in_channels, in_channels, kernel_size=3, deformable_groups=4)
+        last = SmallConv3x3 if num_cls <= 4 else nn.Conv2d
+        self.cls_head = nn.Sequential(*fuse_bn_relu([Conv3x3(in_channels, head_conv, kernel_size=3, padding=1, bias=True),
+                                                     FastBatchNorm2d(64),   # a literal 64 in the reference, not head_conv
+                                                     nn.ReLU(inplace=True),
+                                                     last(head_conv, num_cls, kernel_size=3, stride=1, padding=1, bias=True)]))
+        self.cls_head[-1].bias.data.fill_(init_bias)
+        self.task_head = SepHead(in_channels, heads, head_conv=head_conv, bn=bn, final_kernel=final_kernel)
+
+    def forward(self, x):
+        center_feat = self.feature_adapt_cls(x)
+        reg_feat = self.feature_adapt_reg(x)
+        ret = self.task_head(reg_feat)
+        ret["hm"] = self.cls_head(center_feat)
+        return ret
+
+
 @HEADS.register_module
 class CenterHead(nn.Module):
     def __init__(self, in_channels=[128, ], tasks=[], dataset="nuscenes", weight=0.25, code_weights=[],
@@ -670,7 +717,7 @@ class CenterHead(nn.Module):
                  dcn_head=False):
         super().__init__()
         if dcn_head:
-            raise NotImplementedError("dcn_head=True (nuScenes DCN configs) is outside the Waymo hot path")
+            self.graph_segment = False   # detectors._dense_call: eager launches (the deformable head has no graph-replay tests yet)
         num_classes = [len(t["class_names"]) for t in tasks]
         self.class_names = [t["class_names"] for t in tasks]
         self.code_weights = code_weights
@@ -688,6 +735,9 @@ class CenterHead(nn.Module):
         self.tasks = nn.ModuleList()
         for num_cls in num_classes:
             heads = copy.deepcopy(dict(common_heads))
+            if dcn_head:
+                self.tasks.append(DCNSepHead(share_conv_channel, num_cls, heads, bn=True, init_bias=init_bias, final_kernel=3))
+                continue
             heads.update(dict(hm=(num_cls, num_hm_conv)))
             self.tasks.append(SepHead(share_conv_channel, heads, bn=True, init_bias=init_bias, final_kernel=3))
 

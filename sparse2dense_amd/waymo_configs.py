@@ -7,6 +7,7 @@ det3d_shim.Config.fromfile; these literals exist so that bench.py and the GPU te
   s2d_student()            same file :48-76 (`S_model`)
   second_voxelnet_parts()  configs/waymo/voxelnet/waymo_second_3x_interval_5.py (reader/backbone/neck of config 1)
   second_voxelnet_train()  same file :58-106 with the full head dictionaries (:78-105); SECOND_ASSIGNER :15-55,108-113; SECOND_TEST_CFG :117-130
+  nusc_centerpoint_dcn()   configs/nusc/voxelnet/nusc_centerpoint_voxelnet_0075voxel_dcn.py:6-13,23-55 (`model`: CenterHead with dcn_head=True)
 """
 import logging
 
@@ -127,3 +128,21 @@ def pillar_s2d_student():
     """same file :55-88 (`S_model`) — BASELINE config 5"""
     return dict(type="KD_PointPillars", pretrained=None, reader=_pp_reader(),
                 backbone=dict(type="PointPillarsScatter_S2D", ds_factor=1), neck=_pp_neck(), bbox_head=_pp_head())
+
+
+NUSC_TASKS = [dict(num_class=1, class_names=["car"]), dict(num_class=2, class_names=["truck", "construction_vehicle"]),
+              dict(num_class=2, class_names=["bus", "trailer"]), dict(num_class=1, class_names=["barrier"]),
+              dict(num_class=2, class_names=["motorcycle", "bicycle"]), dict(num_class=2, class_names=["pedestrian", "traffic_cone"])]
+
+
+def nusc_centerpoint_dcn():
+    """configs/nusc/voxelnet/nusc_centerpoint_voxelnet_0075voxel_dcn.py:23-55 (`model`): six tasks with a velocity head, and the
+    deformable feature adaption in front of every task's branches"""
+    return dict(type="VoxelNet", pretrained=None,
+                reader=dict(type="VoxelFeatureExtractorV3", num_input_features=5),
+                backbone=dict(type="SpMiddleResNetFHD", num_input_features=5, ds_factor=8),
+                neck=_neck("RPN"),
+                bbox_head=dict(type="CenterHead", in_channels=sum([256, 256]), tasks=NUSC_TASKS, dataset="nuscenes", weight=0.25,
+                               code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2, 1.0, 1.0],
+                               common_heads={"reg": (2, 2), "height": (1, 2), "dim": (3, 2), "rot": (2, 2), "vel": (2, 2)},
+                               share_conv_channel=64, dcn_head=True))
