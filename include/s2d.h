@@ -711,6 +711,36 @@ int s2d_regloss_bwd(const float *feat, const int64_t *ind, const uint8_t *mask, 
                     int max_objs, const float *res, const float *go, float *dfeat, s2d_stream_t stream);
 
 /*
+ * The two losses for ALL tasks of a CenterHead in one node (the six-task nuScenes head): from the heat-map LOGITS and the branch maps
+ * as the head produced them.  One record per task, passed as a HOST array (it travels in the kernel arguments); every map fp32
+ * contiguous [batch][channels][hw]: hm_logit / hm (target) / p [classes], reg [2], height [1], dim [3], vel [2] (NULL for every task
+ * of a head without a velocity branch: the target columns are then [0..5, 8, 9]), rot [2]; ind, cat int64 and mask uint8
+ * [batch][max_objs]; anno_box fp32 [batch][max_objs][10].  fwd writes p = clamp(sigmoid(hm_logit), 1e-4, 1 - 1e-4), loss / loc_loss
+ * [num_tasks] and res [num_tasks][16] = loss, hm_loss, loc_loss, loc_loss_elem[10], num_positive, 0, 0 with
+ * loss = hm_loss + weight * sum_c code_weights[c] * loc_loss_elem[c] (code_weights: device, 10 floats with vel, else 8).  Same inputs,
+ * same bits.  bwd writes d_logit of every task in full and scatters into d_reg .. d_rot, which must lie inside [dbranch, dbranch +
+ * dbranch_bytes) - zero-filled by the entry; go_loss / go_loc: device [num_tasks] upstream gradients of loss / loc_loss (NULL = zero).
+ */
+typedef struct s2d_center_task {
+    const float *hm_logit, *reg, *height, *dim, *vel, *rot;
+    const float *hm;
+    const int64_t *ind;
+    const uint8_t *mask;
+    const int64_t *cat;
+    const float *anno_box;
+    float *p;
+    float *d_logit, *d_reg, *d_height, *d_dim, *d_vel, *d_rot;   /* bwd only */
+    int classes;
+} s2d_center_task;
+size_t s2d_center_tasks_loss_workspace_bytes(void);
+int s2d_center_tasks_loss_fwd(const s2d_center_task *tasks, int num_tasks, int batch, int64_t hw, int max_objs,
+                              const float *code_weights, float weight, float *loss, float *loc_loss, float *res, void *ws,
+                              size_t ws_bytes, s2d_stream_t stream);
+int s2d_center_tasks_loss_bwd(const s2d_center_task *tasks, int num_tasks, int batch, int64_t hw, int max_objs,
+                              const float *code_weights, float weight, const float *res, const float *go_loss,
+                              const float *go_loc, void *dbranch, size_t dbranch_bytes, s2d_stream_t stream);
+
+/*
  * Feature-distillation loss of the S2D step (det3d/torchie/trainer/trainer.py:783-789): w_pos * MSE over teacher > 0 + w_neg * MSE
  * over the rest, between two dense tensors of n elements (n % 8 == 0) in the SAME memory order, bf16 (flag 1) or fp32 (0) each.
  * out4 (device) = loss, 2*w_pos/n_pos, 2*w_neg/n_neg, n_pos.  bwd: dstudent (student's element type) = go * dloss/dstudent.
@@ -794,6 +824,20 @@ int s2d_assign_label(const float *gt_boxes, const int32_t *gt_classes, int frame
                      int fmap_h, int num_classes, int max_objs, double gaussian_overlap, int min_radius,
                      float *hm_zeroed, float *anno_box, int64_t *ind, uint8_t *mask, int64_t *cat,
                      float *gt_boxes_and_cls, s2d_stream_t stream);
+/*
+ * The same for a table of tasks (AssignLabel with the six-task nuScenes table), from boxes in the frame's ORIGINAL order: gt_classes are
+ * the global 1-based classes (<= 0 or above the last class of the table: ignored), task_num_classes a HOST array of num_tasks (<= 8)
+ * class counts; task t owns the classes off_t+1 .. off_t+n_t.  Slot k of a task is its k-th object in (class, original index) order,
+ * objects with k >= max_objs are dropped.  Outputs are laid out task after task: hm fp32 [frames][n_t][fmap_h][fmap_w] per task at plane
+ * offset frames * off_t (ZEROED by the caller), anno_box fp32 [tasks][frames][max_objs][10], ind int64 / mask uint8 / cat int64 (class
+ * inside the task) [tasks][frames][max_objs] - all fully written - and, optional, gt_boxes_and_cls fp32 [frames][max_objs][10] =
+ * (x,y,z,w,l,h,yaw,vx,vy,global class) over the flattened task order, cut at max_objs rows (the reference asserts that they fit).
+ */
+int s2d_assign_label_tasks(const float *gt_boxes, const int32_t *gt_classes, int frames, int max_boxes,
+                           const int32_t *task_num_classes, int num_tasks, const float pc_range_xy[2],
+                           const float voxel_size_xy[2], int out_size_factor, int fmap_w, int fmap_h, int max_objs,
+                           double gaussian_overlap, int min_radius, float *hm_zeroed, float *anno_box, int64_t *ind,
+                           uint8_t *mask, int64_t *cat, float *gt_boxes_and_cls, s2d_stream_t stream);
 
 /*
  * SECOND anchor head (csrc/anchor_head.hip), Waymo configuration: ground_box3d_coder 7-wide (x,y,z,w,l,h,r), nearest-IoU similarity, no

@@ -16,6 +16,12 @@ _PFN_GEO = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c
 _F3 = ctypes.c_float * 3
 _F6 = ctypes.c_float * 6
 
+
+class CenterTask(ctypes.Structure):
+    """s2d_center_task of include/s2d.h: the maps, targets and gradient maps of one CenterHead task"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("hm_logit", "reg", "height", "dim", "vel", "rot", "hm", "ind", "mask", "cat", "anno_box", "p",
+                                               "d_logit", "d_reg", "d_height", "d_dim", "d_vel", "d_rot")] + [("classes", ctypes.c_int)]
+
 # name -> (restype, argtypes); mirrors include/s2d.h one to one
 SIGNATURES = {
     "s2d_version": (ctypes.c_int, []),
@@ -195,6 +201,11 @@ SIGNATURES = {
                                        c_f32p, ctypes.c_void_p]),
     "s2d_regloss_bwd": (ctypes.c_int, [c_f32p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                        c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "s2d_center_tasks_loss_workspace_bytes": (ctypes.c_size_t, []),
+    "s2d_center_tasks_loss_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_f32p, ctypes.c_float,
+                                                 c_f32p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_center_tasks_loss_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_f32p, ctypes.c_float,
+                                                 c_f32p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "s2d_masked_mse_workspace_bytes": (ctypes.c_size_t, []),
     "s2d_masked_mse_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
                                           c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
@@ -232,6 +243,9 @@ SIGNATURES = {
                                       ctypes.c_size_t, ctypes.c_void_p]),
     "s2d_assign_label": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_float * 2, ctypes.c_float * 2] + [ctypes.c_int] * 5 +
                          [ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 7),
+    "s2d_assign_label_tasks": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                              ctypes.c_float * 2, ctypes.c_float * 2] + [ctypes.c_int] * 4 + [ctypes.c_double, ctypes.c_int] +
+                               [ctypes.c_void_p] * 7),
     "s2d_adam_max_tensors": (ctypes.c_int, []),
     "s2d_adam_step_f32": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float] * 5 + [ctypes.c_int, c_f32p, ctypes.c_void_p]),
     "s2d_grad_norm_workspace_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_void_p]),

@@ -102,6 +102,53 @@ class SyntheticFrames:
         return ex
 
 
+NUSC_TRAIN_MAX_VOXELS = 120000   # configs/nusc/voxelnet/nusc_centerpoint_voxelnet_0075voxel_dcn.py: voxel_generator.max_voxel_num[0]
+# the scene generator's three kinds of objects spread over the ten nuScenes classes (waymo_configs.NUSC_TASKS order, 1-based)
+_NUSC_CLASSES_OF = {1: (1, 2, 3, 4, 5, 6), 2: (9, 10), 3: (7, 8)}
+
+
+class SyntheticNuscFrames(SyntheticFrames):
+    """The same seeded sweeps on the nuScenes grid (0.075 m voxels, 10 points each, range +-54 m: a 180 x 180 map) with the objects
+    relabelled over the ten nuScenes classes, in the scene's original (unsorted) order.  On a CUDA device the six-task targets are
+    assigned there every iteration (targets.assign_label_tasks: hm / anno_box / ind / mask / cat lists with one entry per task, plus
+    gt_boxes_and_cls); on the host they come from scene.assign_targets_tasks once."""
+
+    def __init__(self, batch_size, n_points=150000, seed=20240928, device="cuda", beam_jitter=2e-4, tasks=None, max_objs=500, n_cars=100,
+                 n_peds=40):
+        from .waymo_configs import NUSC_TASKS
+        self.device = torch.device(device)
+        self.distill, self.anchor_targets = False, None
+        self.tasks = NUSC_TASKS if tasks is None else tasks
+        self.max_objs = max_objs
+        self.gens = {"": VoxelGenerator(scene.NUSC_VOXEL, scene.NUSC_RANGE, 10, NUSC_TRAIN_MAX_VOXELS)}
+        self.points, self.dense_points, self.recon_points = [], [], []
+        gt_b, gt_c = [], []
+        for b in range(batch_size):
+            s = scene.make_scene(n_points, seed=seed + b, beam_jitter=beam_jitter, pc_range=scene.NUSC_RANGE, n_cars=n_cars, n_peds=n_peds)
+            self.points.append(torch.from_numpy(s["points"]).to(self.device))
+            rs = np.random.RandomState(seed + 1000 + b)
+            gt_b.append(s["gt_boxes"])
+            gt_c.append(np.array([rs.choice(_NUSC_CLASSES_OF[int(c)]) for c in s["gt_classes"]], np.int32))
+        self.grid_size = self.gens[""].grid_size
+        self._kw = dict(pc_range=scene.NUSC_RANGE, voxel_size=scene.NUSC_VOXEL, out_size_factor=8,
+                        grid_xy=(int(self.grid_size[0]), int(self.grid_size[1])), max_objs=max_objs)
+        if self.device.type == "cuda":
+            from . import targets as _targets
+            self.gt_boxes, self.gt_classes = _targets.pad_boxes(gt_b, gt_c, self.device)
+            self.targets = None
+        else:   # host restatement (tests without a GPU)
+            per_frame = [scene.assign_targets_tasks(b, c, self.tasks, **self._kw) for b, c in zip(gt_b, gt_c)]
+            self.targets = {k: [torch.stack([torch.from_numpy(f[k][t]) for f in per_frame]) for t in range(len(self.tasks))]
+                            for k in ("hm", "anno_box", "ind", "mask", "cat")}
+            self.targets["gt_boxes_and_cls"] = torch.stack([torch.from_numpy(f["gt_boxes_and_cls"]) for f in per_frame])
+
+    def _targets(self):
+        if self.targets is not None:
+            return self.targets
+        from . import targets as _targets
+        return _targets.assign_label_tasks(self.gt_boxes, self.gt_classes, self.tasks, with_boxes_and_cls=True, **self._kw)
+
+
 class SyntheticPillarFrames:
     """Scene C: the same sweeps voxelized as pillars (0.32 m, 20 points, 32 000 pillars,
     configs/waymo/pp/...:156-162) plus the object-only cloud for the PCR target; targets on the

@@ -11,6 +11,7 @@
 training hot path.
 """
 import copy
+import ctypes
 import logging
 import os
 from collections import defaultdict
@@ -111,6 +112,107 @@ class _RegLossFn(torch.autograd.Function):
         _lib.check(_lib.load().s2d_regloss_bwd(_ptr(output), _ptr(ind), _ptr(mask), _ptr(target), b, c, h * w, ind.shape[1], _ptr(res),
                                                _ptr(go.float().contiguous()), _ptr(dfeat), _stream()), "s2d_regloss_bwd")
         return dfeat, None, None, None
+
+
+_BRANCHES = ("reg", "height", "dim", "vel", "rot")
+
+
+def center_fused_loss_ok(example, preds_dicts):
+    """the multi-task node (csrc/center_loss.hip, s2d_center_tasks_loss_*) takes 2..8 tasks with the same branches (reg, height, dim, rot
+    and optionally vel) as CUDA fp32 contiguous maps, and device targets of the reference's dtypes; S2D_CENTER_FUSED_LOSS=0 switches it
+    off"""
+    if os.environ.get("S2D_CENTER_FUSED_LOSS", "1") == "0" or not 1 < len(preds_dicts) <= 8:
+        return False
+    names = {k for k in _BRANCHES if k in preds_dicts[0]}
+    if names | {"vel"} != set(_BRANCHES):
+        return False
+    for t, preds in enumerate(preds_dicts):
+        if {k for k in _BRANCHES if k in preds} != names or not _loss_maps_ok(preds["hm"], example["ind"][t], example["cat"][t]):
+            return False
+        hw = preds["hm"].shape[2:]
+        if not all(preds[k].is_cuda and preds[k].dtype == torch.float32 and preds[k].is_contiguous() and preds[k].shape[2:] == hw for k in names):
+            return False
+        if not (example["hm"][t].is_cuda and example["hm"][t].shape == preds["hm"].shape and example["anno_box"][t].is_cuda
+                and example["anno_box"][t].shape[-1] == 10 and example["ind"][t].shape == example["ind"][0].shape):
+            return False
+    return True
+
+
+class _CenterTasksLossFn(torch.autograd.Function):
+    """FastFocalLoss + RegLoss + the code-weight sum of every task of a CenterHead: 2 launches forward, zero-fill + 2 backward
+    (csrc/center_loss.hip).  apply(n_tasks, n_branches, weight, code_weights, *logits, *branch maps (task-major), *hm, *ind, *mask, *cat,
+    *anno_box) -> (loss[T], loc_loss[T], res[T,16], *p); res and p carry no gradient."""
+
+    @staticmethod
+    def _table(nt, nb, logits, branches, hm, ind, mask, cat, anno, p, grads=None):
+        from . import _lib
+        names = [k for k in _BRANCHES if k != "vel" or nb == 5]
+        tab = (_lib.CenterTask * nt)()
+        for t in range(nt):
+            r = tab[t]
+            r.hm_logit, r.hm, r.ind, r.mask, r.cat = logits[t].data_ptr(), hm[t].data_ptr(), ind[t].data_ptr(), mask[t].data_ptr(), cat[t].data_ptr()
+            r.anno_box, r.p, r.classes = anno[t].data_ptr(), p[t].data_ptr(), logits[t].shape[1]
+            for i, k in enumerate(names):
+                setattr(r, k, branches[t * nb + i].data_ptr())
+            if grads is not None:
+                r.d_logit = grads[0][t].data_ptr()
+                for i, k in enumerate(names):
+                    setattr(r, "d_" + k, grads[1][t * nb + i].data_ptr())
+        return tab
+
+    @staticmethod
+    def forward(ctx, nt, nb, weight, cw, *tensors):
+        from . import _lib
+        from .dense2d import _ptr, _stream, _ws
+        lib = _lib.load()
+        logits, branches = tensors[:nt], tensors[nt:nt + nt * nb]
+        rest = tensors[nt + nt * nb:]
+        hm = [t.float().contiguous() for t in rest[:nt]]
+        ind = [t.contiguous() for t in rest[nt:2 * nt]]
+        mask = [_u8(t).contiguous() for t in rest[2 * nt:3 * nt]]
+        cat = [t.contiguous() for t in rest[3 * nt:4 * nt]]
+        anno = [t.float().contiguous() for t in rest[4 * nt:5 * nt]]
+        dev = logits[0].device
+        b, _, h, w = logits[0].shape
+        p = [torch.empty_like(t) for t in logits]
+        loss = torch.empty(nt, dtype=torch.float32, device=dev)
+        loc = torch.empty(nt, dtype=torch.float32, device=dev)
+        res = torch.empty((nt, 16), dtype=torch.float32, device=dev)
+        ws = _ws(lib.s2d_center_tasks_loss_workspace_bytes(), dev)
+        tab = _CenterTasksLossFn._table(nt, nb, logits, branches, hm, ind, mask, cat, anno, p)
+        _lib.check(lib.s2d_center_tasks_loss_fwd(ctypes.addressof(tab), nt, b, h * w, ind[0].shape[1], _ptr(cw), float(weight), _ptr(loss), _ptr(loc),
+                                                 _ptr(res), _ptr(ws), ws.numel(), _stream()), "s2d_center_tasks_loss_fwd")
+        ctx.nt, ctx.nb, ctx.weight = nt, nb, float(weight)
+        ctx.save_for_backward(cw, res, *logits, *branches, *hm, *ind, *mask, *cat, *anno, *p)
+        ctx.mark_non_differentiable(res, *p)
+        ctx.set_materialize_grads(False)
+        return (loss, loc, res, *p)
+
+    @staticmethod
+    def backward(ctx, go_loss, go_loc, *_):
+        from . import _lib
+        from .dense2d import _ptr, _stream
+        nt, nb = ctx.nt, ctx.nb
+        cw, res, *t = ctx.saved_tensors
+        logits, branches = t[:nt], t[nt:nt + nt * nb]
+        hm, ind, mask, cat, anno, p = (t[nt + nt * nb + i * nt:nt + nt * nb + (i + 1) * nt] for i in range(6))
+        none = (None,) * (4 + len(t) - nt)
+        if go_loss is None and go_loc is None:
+            return none
+        b, _, h, w = logits[0].shape
+        dlogit = [torch.empty_like(x) for x in logits]
+        flat = torch.empty(sum(x.numel() for x in branches), dtype=torch.float32, device=res.device)   # zero-filled by the entry
+        dbr, at = [], 0
+        for x in branches:
+            dbr.append(flat[at:at + x.numel()].view(x.shape))
+            at += x.numel()
+        tab = _CenterTasksLossFn._table(nt, nb, logits, branches, hm, ind, mask, cat, anno, p, grads=(dlogit, dbr))
+        go_loss = None if go_loss is None else go_loss.float().contiguous()
+        go_loc = None if go_loc is None else go_loc.float().contiguous()
+        _lib.check(_lib.load().s2d_center_tasks_loss_bwd(ctypes.addressof(tab), nt, b, h * w, ind[0].shape[1], _ptr(cw), ctx.weight, _ptr(res),
+                                                         _ptr(go_loss), _ptr(go_loc), _ptr(flat), flat.numel() * 4, _stream()),
+                   "s2d_center_tasks_loss_bwd")
+        return (None, None, None, None, *dlogit, *dbr) + (None,) * (5 * nt)
 
 
 def fast_focal_loss(out, target, ind, mask, cat):
@@ -749,7 +851,41 @@ class CenterHead(nn.Module):
     def _sigmoid(x):
         return torch.clamp(x.sigmoid_(), min=1e-4, max=1 - 1e-4)
 
+    def _code_weights(self, like):
+        cw = getattr(self, "_code_w", None)   # device copy of the code weights, made once (an H2D copy per step is also not capturable)
+        if cw is None or cw.device != like.device or cw.dtype != like.dtype or cw.numel() != len(self.code_weights):
+            cw = self._code_w = like.new_tensor(self.code_weights)
+        return cw
+
+    def _loss_fused(self, example, preds_dicts):
+        """every task in one autograd node (_CenterTasksLossFn).  Same dict as the per-task loop below: lists with one entry per task,
+        hm_loss / loc_loss_elem / num_positive without a graph, device scalars.  preds["hm"] becomes the stored clamped sigmoid map,
+        detached (the logits are NOT overwritten in place); preds["anno_box"] is not set - only the Waymo distillation trainer reads
+        it, and a one-task head never takes this path."""
+        nt = len(preds_dicts)
+        names = [k for k in _BRANCHES if k in preds_dicts[0]]
+        cw = self._code_weights(preds_dicts[0]["hm"])
+        if cw.numel() != (10 if "vel" in names else 8):
+            raise ValueError(f"CenterHead.loss: {cw.numel()} code weights for the branches {names}")
+        args = [p["hm"] for p in preds_dicts] + [p[k] for p in preds_dicts for k in names]
+        for key in ("hm", "ind", "mask", "cat", "anno_box"):
+            args += [example[key][t] for t in range(nt)]
+        loss, loc, res, *probs = _CenterTasksLossFn.apply(nt, len(names), self.weight, cw, *args)
+        for preds, p in zip(preds_dicts, probs):
+            preds["hm"] = p
+        merged = defaultdict(list)
+        merged["loss"], merged["loc_loss"] = list(loss.unbind(0)), list(loc.unbind(0))
+        rows = res.unbind(0)
+        merged["hm_loss"] = [r[1] for r in rows]
+        merged["loc_loss_elem"] = [r[3:3 + cw.numel()] for r in rows]
+        merged["num_positive"] = [r[13] for r in rows]
+        return merged
+
     def loss(self, example, preds_dicts, **kwargs):
+        if len(self.tasks) > 1 and center_fused_loss_ok(example, preds_dicts):
+            if self.dataset not in ("waymo", "nuscenes"):
+                raise NotImplementedError()
+            return self._loss_fused(example, preds_dicts)
         merged = defaultdict(list)
         for task_id, preds in enumerate(preds_dicts):
             preds["hm"] = self._sigmoid(preds["hm"])
@@ -766,9 +902,7 @@ class CenterHead(nn.Module):
                 # HIP-graph capture also refuses)
                 target_box = torch.cat((target_box[..., :6], target_box[..., -2:]), -1)
             box_loss = self.crit_reg(preds["anno_box"], example["mask"][task_id], example["ind"][task_id], target_box)
-            cw = getattr(self, "_code_w", None)   # device copy of the code weights, made once (an H2D copy per step is also not capturable)
-            if cw is None or cw.device != box_loss.device or cw.dtype != box_loss.dtype or cw.numel() != len(self.code_weights):
-                cw = self._code_w = box_loss.new_tensor(self.code_weights)
+            cw = self._code_weights(box_loss)
             loc_loss = (box_loss * cw).sum()
             loss = hm_loss + self.weight * loc_loss
             # NB: the reference copies the logging scalars to the host here (.detach().cpu(), four

@@ -16,6 +16,10 @@ WAYMO_VOXEL = (0.1, 0.1, 0.15)
 PILLAR_RANGE = (-74.88, -74.88, -2.0, 74.88, 74.88, 4.0)
 PILLAR_VOXEL = (0.32, 0.32, 6.0)
 WAYMO_BEAM_JITTER = 2.5e-3   # see make_scene(beam_jitter=...)
+# configs/nusc/voxelnet/nusc_centerpoint_voxelnet_0075voxel_dcn.py: 1440 x 1440 x 40 voxels, a 180 x 180 map at out_size_factor 8
+NUSC_RANGE = (-54.0, -54.0, -5.0, 54.0, 54.0, 3.0)
+NUSC_VOXEL = (0.075, 0.075, 0.2)
+NUSC_GRID_XY = (1440, 1440)
 
 
 def _ray_box(origin, dirs, center, size, yaw):
@@ -236,3 +240,53 @@ def assign_targets(gt_boxes, gt_classes, pc_range=WAYMO_RANGE, voxel_size=WAYMO_
         anno_box[k] = np.concatenate((ct - (x, y), box[2], np.log(box[3:6]), box[6], box[7],
                                       np.sin(yaw), np.cos(yaw)), axis=None)
     return dict(hm=hm, anno_box=anno_box, ind=ind, mask=mask, cat=cat)
+
+
+def task_class_counts(tasks):
+    """per-task class counts of a config's task table (dicts with `num_class` / `class_names`, or plain ints)"""
+    out = []
+    for t in tasks:
+        if isinstance(t, (int, np.integer)):
+            out.append(int(t))
+        elif "num_class" in t:
+            out.append(int(t["num_class"]))
+        else:
+            out.append(len(t["class_names"]))
+    if not out or min(out) < 1:
+        raise ValueError(f"task table {out}: every task needs at least one class")
+    return out
+
+
+def assign_targets_tasks(gt_boxes, gt_classes, tasks, pc_range=NUSC_RANGE, voxel_size=NUSC_VOXEL, out_size_factor=8,
+                         grid_xy=NUSC_GRID_XY, max_objs=500, gaussian_overlap=0.1, min_radius=2):
+    """AssignLabel for a table of tasks (preprocess.py:489-653), one frame.  gt_classes are the GLOBAL 1-based classes in the frame's
+    original order (<= 0 or above the table's last class: ignored).  Task t owns the classes off_t+1 .. off_t+n_t; its object list is
+    the `np.where` per class, concatenated (class within the task, then original index), cut at max_objs.  Returns lists with one entry
+    per task - hm f32[n_t,H,W], anno_box f32[max_objs,10], ind i64, mask u8, cat i64 (local class) - and gt_boxes_and_cls
+    f32[max_objs,10] = (x,y,z,w,l,h,yaw,vx,vy,global class) over the flattened task order (the reference asserts that all objects fit
+    into max_objs rows; here the list is cut)."""
+    counts = task_class_counts(tasks)
+    gt_boxes = np.asarray(gt_boxes, np.float32).reshape(-1, 9)
+    gt_classes = np.asarray(gt_classes).reshape(-1)
+    out = {k: [] for k in ("hm", "anno_box", "ind", "mask", "cat")}
+    flat_boxes, flat_classes = [], []
+    off = 0
+    for n_t in counts:
+        order = np.concatenate([np.where(gt_classes == off + c + 1)[0] for c in range(n_t)])
+        boxes_t, classes_t = gt_boxes[order], gt_classes[order].astype(np.int32) - off
+        t = assign_targets(boxes_t, classes_t, pc_range=pc_range, voxel_size=voxel_size, out_size_factor=out_size_factor,
+                           num_classes=n_t, max_objs=max_objs, gaussian_overlap=gaussian_overlap, min_radius=min_radius, grid_xy=grid_xy)
+        for k in out:
+            out[k].append(t[k])
+        flat_boxes.append(boxes_t)
+        flat_classes.append(classes_t + off)
+        off += n_t
+    boxes = np.concatenate(flat_boxes, 0)
+    if len(boxes):
+        boxes[:, -1] = boxes[:, -1] - np.floor(boxes[:, -1] / (np.pi * 2) + 0.5) * (np.pi * 2)
+    rows = np.concatenate((boxes, np.concatenate(flat_classes).reshape(-1, 1).astype(np.float32)), axis=1)[:, [0, 1, 2, 3, 4, 5, 8, 6, 7, 9]]
+    bc = np.zeros((max_objs, 10), np.float32)
+    n = min(len(rows), max_objs)
+    bc[:n] = rows[:n]
+    out["gt_boxes_and_cls"] = bc
+    return out
