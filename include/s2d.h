@@ -813,6 +813,60 @@ int s2d_nms_circle(const float *xy_sorted, int n, float thresh, int max_keep, in
                    s2d_stream_t stream);
 
 /*
+ * CenterHead.predict on the device for ALL tasks and samples of a head at once (csrc/center_predict.hip).  A SEGMENT is one
+ * (task, sample) pair, segment = task * samples + sample.  One record per task, passed as a HOST array of 1..8 entries (it travels in
+ * the kernel arguments): the fp32 maps hm [classes], reg [2], height [1], dim [3], vel [2] (NULL for every task of a head without a
+ * velocity branch: boxes then have 7 floats, else 9), rot [2], each [images][channels][h][w] with images = samples (4 * samples with
+ * double_flip: every sample as original, H-mirrored, W-mirrored, both), image stride channels * h * w, and element (c, pixel) at
+ * c * channel_stride + pixel * pixel_stride - NCHW-contiguous (h * w, 1) and channels_last (1, channels) maps are read in place.
+ *
+ * s2d_center_predict_score replaces det3d/models/bbox_heads/center_head.py:311-362,384-401 (permute, flips, sigmoid, the means, the
+ * centre) and :459-465 (maximum over classes, score and centre-range masks): score [segments][h * w] = the class maximum of
+ * mean(sigmoid(hm)) or -inf where `score > score_threshold` is false (NaN included) or the centre (x, y, z) lies outside range6 (HOST,
+ * xmin ymin zmin xmax ymax zmax, inclusive; NULL = no test); label [segments][h * w] = its class (lowest index on a tie); count
+ * [segments] = passing pixels.  x = (col + reg_x) * out_size_factor * voxel_x + pc_x, y likewise from the row.
+ *
+ * s2d_center_predict_boxes replaces center_head.py:344,364-382,403-419 (exp, rotation and velocity sign rules, atan2, cat) and the
+ * mask / sort gathers of :467-471,483-485 for the candidates only: with order / score_sorted [segments][h * w] the descending stable
+ * sort of `score` along its last axis, rank r < min(counts[s], max_count) of segment s becomes row offsets[s] + r of the packed
+ * lists boxes [total][7 or 9] = x, y, z, mean(exp(dim)), (vel,) atan2(rot_sin, rot_cos); scores [total]; labels [total] (int64, class +
+ * label_base of the task).  offsets / counts: DEVICE int32 [segments]; rows outside [0, total) are not written.
+ */
+#define S2D_CENTER_PREDICT_MAX_TASKS 8
+typedef struct s2d_center_predict_task {
+    const float *map[6];   /* hm, reg, height, dim, vel, rot */
+    int64_t channel_stride[6], pixel_stride[6];
+    int classes;
+    int label_base;
+} s2d_center_predict_task;
+int s2d_center_predict_score(const s2d_center_predict_task *tasks, int num_tasks, int samples, int h, int w, int double_flip,
+                             float score_threshold, const float *range6, float out_size_factor, float voxel_x, float voxel_y, float pc_x,
+                             float pc_y, float *score, int32_t *label, int32_t *count, s2d_stream_t stream);
+int s2d_center_predict_boxes(const s2d_center_predict_task *tasks, int num_tasks, int samples, int h, int w, int double_flip,
+                             float out_size_factor, float voxel_x, float voxel_y, float pc_x, float pc_y, const int64_t *order,
+                             const float *score_sorted, const int32_t *label, const int32_t *offsets, const int32_t *counts, int max_count,
+                             int64_t total, float *boxes, float *scores, int64_t *labels, s2d_stream_t stream);
+
+/*
+ * The two greedy NMS forms above for MANY independent segments in two launches; replaces the per-(task, sample) loop of
+ * center_head.py:455-481 over box_torch_ops.py:449-464 (rotate_nms_pcdet) / center_head.py:499-507 (_circle_nms): one kernel fills the
+ * suppression bits of every segment, one walks them with a workgroup per segment.  Segment s = rows offsets[s] .. offsets[s] +
+ * min(counts[s], max_count) of a packed list of `total` rows sorted by descending score inside each segment (DEVICE int32 arrays;
+ * max_count <= 65536; a segment reaching outside [0, total) counts as empty).  Rotated form: rows of box_stride >= 7 floats, x y z dx dy
+ * dz first and the heading LAST (7- and 9-float boxes alike).  Circle form: (x, y) first in rows of xy_stride floats, thresh DEVICE
+ * [segments] (test_cfg.min_radius of the segment's task, compared with the squared distance as the reference does).
+ * Outputs: keep [segments][max_keep] int64 indices into the segment's own rows, n_keep [segments] - written for EVERY segment, empty
+ * ones included; keep entries past n_keep[s] are left untouched.  Workspace: s2d_nms_batched_workspace_bytes(total, max_count).
+ */
+size_t s2d_nms_batched_workspace_bytes(int64_t total, int max_count);
+int s2d_nms_rotated_bev_batched(const float *boxes, int box_stride, const int32_t *offsets, const int32_t *counts, int segments,
+                                int max_count, int64_t total, float iou_threshold, int max_keep, int64_t *keep, int32_t *n_keep, void *ws,
+                                size_t ws_bytes, s2d_stream_t stream);
+int s2d_nms_circle_batched(const float *xy, int xy_stride, const int32_t *offsets, const int32_t *counts, int segments, int max_count,
+                           int64_t total, const float *thresh, int max_keep, int64_t *keep, int32_t *n_keep, void *ws, size_t ws_bytes,
+                           s2d_stream_t stream);
+
+/*
  * CenterPoint training targets on the device = AssignLabel.__call__ (det3d/datasets/pipelines/preprocess.py:489-653, one-task
  * Waymo head) with gaussian_radius / draw_umich_gaussian (det3d/core/utils/center_utils.py:18-64).  gt_boxes fp32
  * [frames][max_boxes][9] (x,y,z,w,l,h,vx,vy,yaw), gt_classes int32 [frames][max_boxes] (1-based, <= 0 = padding).  Outputs per

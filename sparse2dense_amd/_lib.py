@@ -22,6 +22,12 @@ class CenterTask(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("hm_logit", "reg", "height", "dim", "vel", "rot", "hm", "ind", "mask", "cat", "anno_box", "p",
                                                "d_logit", "d_reg", "d_height", "d_dim", "d_vel", "d_rot")] + [("classes", ctypes.c_int)]
 
+class CenterPredictTask(ctypes.Structure):
+    """s2d_center_predict_task of include/s2d.h: the six maps of one CenterHead task (hm, reg, height, dim, vel, rot) with their strides"""
+    _fields_ = [("map", ctypes.c_void_p * 6), ("channel_stride", ctypes.c_int64 * 6), ("pixel_stride", ctypes.c_int64 * 6),
+                ("classes", ctypes.c_int), ("label_base", ctypes.c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/s2d.h one to one
 SIGNATURES = {
     "s2d_version": (ctypes.c_int, []),
@@ -241,6 +247,15 @@ SIGNATURES = {
                                            ctypes.c_size_t, ctypes.c_void_p]),
     "s2d_nms_circle": (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_center_predict_score": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p] + [ctypes.c_float] * 5 +
+                                 [ctypes.c_void_p] * 4),
+    "s2d_center_predict_boxes": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_float] * 5 + [ctypes.c_void_p] * 5 +
+                                 [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    "s2d_nms_batched_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "s2d_nms_rotated_bev_batched": (ctypes.c_int, [c_f32p, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
+                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_nms_circle_batched": (ctypes.c_int, [c_f32p, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_f32p,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "s2d_assign_label": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_float * 2, ctypes.c_float * 2] + [ctypes.c_int] * 5 +
                          [ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 7),
     "s2d_assign_label_tasks": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,

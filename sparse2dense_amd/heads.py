@@ -7,8 +7,8 @@
   distillation losses              /root/reference/det3d/torchie/trainer/trainer.py:38-76,783-805
   mask_offset_loss                 /root/reference/det3d/models/detectors/voxelnet.py:171-185
 
-`CenterHead.predict` (decode + rotated NMS) is inference post-processing and out of scope of the
-training hot path.
+`CenterHead.predict` (decode + rotated / circle NMS) runs on the device through center_predict.py for CUDA
+maps; `CenterHead.predict_torch` is the per-segment torch chain it replaced.
 """
 import copy
 import ctypes
@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import center_predict
 from .dcn import DeformConv
 from .dense2d import Conv3x3, FastBatchNorm2d, SmallConv3x3, fuse_bn_relu
 from .registry import HEADS, LOSSES
@@ -832,6 +833,7 @@ class CenterHead(nn.Module):
         self.box_n_dim = 9 if "vel" in common_heads else 7
         self.use_direction_classifier = False
         self.logger = logger or logging.getLogger("CenterHead")
+        self.predict_paths = {"device": 0, "torch": 0}   # calls of predict() by the path they took
         self.shared_conv = nn.Sequential(*fuse_bn_relu([Conv3x3(in_channels, share_conv_channel, 3, padding=1, bias=True),
                                                         FastBatchNorm2d(share_conv_channel), nn.ReLU(inplace=True)]))
         self.tasks = nn.ModuleList()
@@ -922,6 +924,33 @@ class CenterHead(nn.Module):
         sin / cos and the velocities with the flipped components negated) before the boxes are built (center_head.py:343-381,402-412).
         test_cfg.circular_nms (r06): centre-distance NMS with min_radius[task] instead of the rotated-IoU NMS (center_head.py:476-479).
         per_class_nms: the reference's branch is `pass` (center_head.py:417-418: no result is produced) - not supported."""
+        get = (lambda k, d=None: test_cfg.get(k, d)) if hasattr(test_cfg, "get") else (lambda k, d=None: getattr(test_cfg, k, d))
+        if get("per_class_nms", False):
+            raise NotImplementedError("CenterHead.predict: per_class_nms produces no result in the reference either (center_head.py:417-418)")
+        # the device path (center_predict.py: every task and sample in a handful of launches and two host reads) whenever it applies;
+        # S2D_CENTER_DEVICE_PREDICT=0 keeps the per-segment torch chain.  predict_paths counts the calls each took.
+        if (1 <= len(preds_dicts) <= center_predict.MAX_TASKS and all(v.is_cuda for p in preds_dicts for v in p.values())
+                and os.environ.get("S2D_CENTER_DEVICE_PREDICT") != "0"):
+            out = self._predict_device(example, preds_dicts, test_cfg, get)
+            if out is not None:   # (None: a segment above the NMS kernels' 65536 boxes, or their workspace above its bound - the whole call takes the chain)
+                self.predict_paths["device"] += 1
+                return out
+        self.predict_paths["torch"] += 1
+        return self.predict_torch(example, preds_dicts, test_cfg, **kwargs)
+
+    def _predict_device(self, example, preds_dicts, test_cfg, get):
+        per_sample = center_predict.predict_on_device(preds_dicts, test_cfg, self.num_classes)
+        if per_sample is None:
+            return None
+        meta = example.get("metadata") if isinstance(example, dict) else None
+        if meta and get("double_flip", False):
+            meta = meta[:4 * len(per_sample):4]
+        return [dict(box3d_lidar=b, scores=s, label_preds=l, metadata=meta[i] if meta else None) for i, (b, s, l) in enumerate(per_sample)]
+
+    @torch.no_grad()
+    def predict_torch(self, example, preds_dicts, test_cfg, **kwargs):
+        """the per-task, per-sample torch chain of `predict` (what it was before the device path, and what runs for CPU maps, more than 8
+        tasks or S2D_CENTER_DEVICE_PREDICT=0)"""
         get = (lambda k, d=None: test_cfg.get(k, d)) if hasattr(test_cfg, "get") else (lambda k, d=None: getattr(test_cfg, k, d))
         if get("per_class_nms", False):
             raise NotImplementedError("CenterHead.predict: per_class_nms produces no result in the reference either (center_head.py:417-418)")

@@ -61,3 +61,51 @@ def circle_nms(centers_xy, scores, min_radius, post_max_size=83):
     _lib.check(lib.s2d_nms_circle(xy.data_ptr(), n, float(min_radius), max_keep, keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _stream(xy.device)), "s2d_nms_circle")
     return order[keep[:int(n_keep.item())]]
+
+
+def _nms_batched(entry, what, rows, segments, counts, thresh, post_max_size):
+    if not rows.is_cuda or not segments.is_cuda:
+        raise _lib.S2DError(f"{what}: CUDA tensors expected (no CPU fallback)")
+    lib = _lib.load()
+    segs = len(counts)
+    if segments.dtype != torch.int32 or tuple(segments.shape) != (2, segs) or not segments.is_contiguous():
+        raise _lib.S2DError(f"{what}: segments must be a contiguous int32 [2, {segs}] tensor (offsets, counts)")
+    rows = rows.float().contiguous()
+    dev = rows.device
+    total, max_count = int(rows.shape[0]), max(counts, default=0)
+    max_keep = max_count if post_max_size is None else min(max_count, int(post_max_size))
+    keep = torch.empty((segs, max_keep), dtype=torch.int64, device=dev)
+    n_keep = torch.empty((segs,), dtype=torch.int32, device=dev)
+    if segs == 0:
+        return keep, []
+    ws = torch.empty(lib.s2d_nms_batched_workspace_bytes(total, max_count), dtype=torch.uint8, device=dev)
+    _lib.check(getattr(lib, entry)(rows.data_ptr(), rows.shape[1] if rows.dim() == 2 else 0, segments[0].data_ptr(), segments[1].data_ptr(), segs,
+                                   max_count, total, thresh, max_keep, keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream(dev)), entry)
+    return keep, n_keep.tolist()
+
+
+def rotate_nms_batched(boxes, segments, counts, thresh, post_max_size=None):
+    """`rotate_nms` for many independent segments in two launches (s2d_nms_rotated_bev_batched): the per-(task, sample) loop of
+    /root/reference/det3d/models/bbox_heads/center_head.py:455-481 over box_torch_ops.py:449-464.
+    boxes: cuda fp32 [N, 7 or more] packed rows (x, y, z, dx, dy, dz, ..., heading LAST), each segment's rows contiguous and already sorted
+    by descending score (a pre_maxsize cut is made by the caller: pass the rows that take part); segments: cuda int32 [2, S] = row
+    offsets and row counts; counts: the same counts on the host (a list - they size the launch, each at most 65536).
+    Returns (keep, n_keep): keep cuda int64 [S, max_keep] indices into each segment's own rows in descending-score order, of which the
+    first n_keep[s] (a host list: the one host read) are valid; max_keep = min(max(counts), post_max_size).  Current stream."""
+    return _nms_batched("s2d_nms_rotated_bev_batched", "rotate_nms_batched", boxes, segments, counts, float(thresh), post_max_size)
+
+
+def circle_nms_batched(centers_xy, segments, counts, min_radius, post_max_size=83):
+    """`circle_nms` for many independent segments in two launches (s2d_nms_circle_batched; center_head.py:473-476,499-507 over
+    core/utils/circle_nms_jit.py:4-31).  centers_xy: cuda fp32 [N, 2 or more] packed rows with (x, y) first - the packed box list
+    itself will do; min_radius: one threshold per segment (a sequence of S floats, or a cuda fp32 [S] tensor), compared with the
+    SQUARED centre distance as the reference does.  segments, counts and the result as `rotate_nms_batched`."""
+    if not centers_xy.is_cuda:
+        raise _lib.S2DError("circle_nms_batched: CUDA tensors expected (no CPU fallback)")
+    if not torch.is_tensor(min_radius):
+        min_radius = torch.tensor([float(r) for r in min_radius], dtype=torch.float32).to(centers_xy.device)
+    if min_radius.numel() != len(counts):
+        raise _lib.S2DError(f"circle_nms_batched: {min_radius.numel()} radii for {len(counts)} segments")
+    radius = min_radius.float().contiguous()
+    return _nms_batched("s2d_nms_circle_batched", "circle_nms_batched", centers_xy, segments, counts, radius.data_ptr(), post_max_size)
