@@ -1111,6 +1111,60 @@ int s2d_deform_conv_wgrad_nhwc_bf16(const void *x, const void *offset, int offse
                                     int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int dil, int dg, float *dweight,
                                     void *ws, size_t ws_bytes, s2d_stream_t stream);
 
+/*
+ * Two-stage RoI path on the device (csrc/roi_head.hip): what det3d/models/detectors/two_stage.py:50-199 does between the first stage's
+ * predict and the RoI MLP, and behind the MLP at inference.  B samples, `cap` RoI slots per sample (NMS_POST_MAXSIZE); boxes are
+ * (x, y, z, w, l, h, yaw).  Everything is fp32 in the torch chain's expression order; one launch per entry, no workspace.
+ *
+ * s2d_roi_pack (two_stage.py:76-122, reorder_first_stage_pred_and_feature without the features): the packed first-stage lists boxes
+ * [total][box_dim] (heading LAST), scores [total], labels [total] int64, sample b's rows being offsets[b] .. offsets[b + 1] (HOST int32
+ * [B + 1], B <= S2D_ROI_MAX_BATCH: they travel in the kernel arguments), become rois [B][cap][7], roi_scores [B][cap], roi_labels
+ * [B][cap] int64 = label + 1; the slots behind a sample's rows are all zero (label 0), rows behind `cap` are dropped.
+ *
+ * s2d_roi_bev_features (two_stage.py:50-74 get_box_center, bird_eye_view.py:9-41, center_utils.py:93-122): feats [B][cap][num_point *
+ * channels] fp32 = the bilinear samples of the map at the box centre (num_point 1) or at the centre and the four face centres
+ * (num_point 5) of box row[b][slot], point 0's channels first; a -1 slot is written as zeros.  The map is read in place: element
+ * (b, c, y, x) at b * stride_b + c * stride_c + y * stride_h + x * stride_w ELEMENTS from `map`, map_dtype 0 fp32 / 1 bf16 (widened
+ * before the multiply).  Cell coordinate = (p - pc) / voxel / out_stride as two divisions; neighbours clamped to the map, weights from
+ * the clamped neighbours, the four products summed in the reference's order.  Contiguous channels (stride_c 1, channels_last) with 16-byte
+ * aligned rows take 16-byte loads; every other layout and channel count is read element by element.
+ *
+ * s2d_roi_match_gt (proposal_target_layer.py:74-104,208-237 over iou3d_nms_utils.py:28-70): gt [B][num_gt][gt_dim], the box in the
+ * first 7 columns and the class in the LAST, num_gt <= S2D_ROI_MAX_GT.  Per sample the valid rows are 0 .. the last row whose fp32
+ * column sum (all gt_dim columns, left to right) is not 0, at least row 0; gt_count [B] int32 = their number.  max_iou [B][cap] = the
+ * largest 3-D IoU (rotated BEV overlap x height overlap / max(vol_a + vol_b - overlap, 1e-6)) of the RoI with the valid rows - with
+ * by_class only rows whose class equals roi_labels - and assignment [B][cap] int64 = that row (the lowest on a tie); a RoI without a
+ * row of its class gets 0 and row 0.
+ *
+ * s2d_roi_targets (ProposalTargetLayer.forward behind the sampling + RoIHead.assign_targets, roi_head_template.py:43-92): idx [B][per]
+ * int32 = the sampled slots.  Gathers out_rois [B][per][7], out_labels int64, out_scores, out_iou, gt_of_rois_src [B][per][8] (7 box
+ * columns + the class of row `assignment`), and writes gt_of_rois [B][per][8] (the residual in the RoI's frame: limit_period, the
+ * subtraction, the rotation, the heading flip and clamp; the class column unchanged), reg_valid_mask int64 = iou > reg_fg_thresh, and
+ * rcnn_cls_labels: cls_score_type 0 "cls" int64 (1 above cls_fg_thresh, -1 between the thresholds, else 0), 1 "roi_iou" fp32
+ * (1 above, 0 below cls_bg_thresh, (iou - bg) / (fg - bg) between).  roi_dim must be 7.
+ *
+ * s2d_roi_refine (roi_head_template.py:153-183 generate_predicted_boxes + two_stage.py:124-150 post_process): n = B * cap RoIs;
+ * boxes [n][7] = the residual rcnn_reg [n][7] plus the RoI's size and heading, rotated by its yaw and moved to its centre; scores [n] =
+ * sqrt(sigmoid(rcnn_cls) * roi_score); labels [n] int64 = roi_label - 1 (-1 on the padding, which the caller slices off).
+ */
+#define S2D_ROI_MAX_GT 512
+#define S2D_ROI_MAX_BATCH 64
+int s2d_roi_pack(const float *boxes, const float *scores, const int64_t *labels, int box_dim, const int32_t *offsets, int batch, int cap,
+                 float *rois, float *roi_scores, int64_t *roi_labels, s2d_stream_t stream);
+int s2d_roi_bev_features(const void *map, int map_dtype, int batch, int channels, int h, int w, int64_t stride_b, int64_t stride_c,
+                         int64_t stride_h, int64_t stride_w, const float *boxes, int64_t total, int box_dim, const int32_t *row, int cap,
+                         int num_point, float pc_x, float pc_y, float voxel_x, float voxel_y, float out_stride, float *feats,
+                         s2d_stream_t stream);
+int s2d_roi_match_gt(const float *rois, const int64_t *roi_labels, int batch, int cap, const float *gt, int num_gt, int gt_dim, int by_class,
+                     float *max_iou, int64_t *assignment, int32_t *gt_count, s2d_stream_t stream);
+int s2d_roi_targets(const int32_t *idx, int batch, int per, int cap, int roi_dim, const float *rois, const int64_t *roi_labels,
+                    const float *roi_scores, const float *max_iou, const int64_t *assignment, const float *gt, int num_gt, int gt_dim,
+                    double reg_fg_thresh, double cls_fg_thresh, double cls_bg_thresh, int cls_score_type, float *out_rois, int64_t *out_labels,
+                    float *out_scores, float *out_iou, float *gt_of_rois_src, float *gt_of_rois, int64_t *reg_valid_mask,
+                    void *rcnn_cls_labels, s2d_stream_t stream);
+int s2d_roi_refine(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *rcnn_cls, const float *rcnn_reg,
+                   int64_t n, float *boxes, float *scores, int64_t *labels, s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

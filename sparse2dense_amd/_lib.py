@@ -421,6 +421,17 @@ SIGNATURES = {
     "s2d_deform_conv_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 10),
     "s2d_deform_conv_wgrad_nhwc_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] +
                                         [ctypes.c_int] * 11 + [c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # two-stage RoI path (csrc/roi_head.hip)
+    "s2d_roi_pack": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int] +
+                     [ctypes.c_void_p] * 4),
+    "s2d_roi_bev_features": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_int64] * 4 +
+                             [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_float] * 5 +
+                             [ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_roi_match_gt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 3 +
+                         [ctypes.c_void_p] * 4),
+    "s2d_roi_targets": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int] +
+                        [ctypes.c_double] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 9),
+    "s2d_roi_refine": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 4),
 }
 
 _lib = None

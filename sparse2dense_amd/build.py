@@ -26,7 +26,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # deform_conv.hip is built the same way for the same reason: its fp32 bilinear blend (four products and three sums per channel) is a
 # packed-FP32 candidate, and its weight-gradient launch runs on the side stream beside the chain's MFMA kernels (rule 36).
 # center_predict.hip too: CenterHead.predict produces the proposals inside every two-stage training step, beside the side stream (rule 36).
-EXTRA = {"deform_conv.hip": ["-fno-slp-vectorize"], "center_predict.hip": ["-fno-slp-vectorize"]}
+# roi_head.hip likewise: its fp32 bilinear blends run in the same step, right behind predict (rule 36).
+EXTRA = {"deform_conv.hip": ["-fno-slp-vectorize"], "center_predict.hip": ["-fno-slp-vectorize"], "roi_head.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("S2D_BUILD_LOSSES_SLP") != "1":
     EXTRA["losses.hip"] = ["-fno-slp-vectorize"]
 

@@ -52,8 +52,11 @@ __host__ __device__ inline bool seg_intersect(const P2 &p1, const P2 &p0, const 
     return true;
 }
 
-__host__ __device__ inline float bev_overlap(const float *a, const float *b) {
-    P2 ca[5], cb[5], pts[16];
+// `pts` holds the (at most 16) polygon points: anything indexable that yields P2 lvalues - a local array, or a view of per-lane LDS
+// rows for a kernel that must stay out of scratch memory (roi_head.hip)
+template <typename Points>
+__host__ __device__ inline float bev_overlap_with(const float *a, const float *b, Points &&pts) {
+    P2 ca[5], cb[5];
     rect_corners(a, ca);
     rect_corners(b, cb);
     int cnt = 0;
@@ -81,6 +84,11 @@ __host__ __device__ inline float bev_overlap(const float *a, const float *b) {
     for (int k = 0; k < cnt - 1; ++k)
         area += (pts[k].x - pts[0].x) * (pts[k + 1].y - pts[0].y) - (pts[k].y - pts[0].y) * (pts[k + 1].x - pts[0].x);
     return fabsf(area) / 2.0f;
+}
+
+__host__ __device__ inline float bev_overlap(const float *a, const float *b) {
+    P2 pts[16];
+    return bev_overlap_with(a, b, pts);
 }
 
 __host__ __device__ inline float bev_iou(const float *a, const float *b) {

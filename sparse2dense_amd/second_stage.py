@@ -18,14 +18,27 @@ checkpoints load through checkpoint.load_state_dict.  Inference path (`return_lo
 Training path (`return_loss=True`, two_stage.py:154-199): the same first stage with its loss, then the RoIs are matched to the
 ground truth by 3-D IoU (rotated BEV overlap from csrc/nms.hip x height overlap), sampled into ROI_PER_IMAGE foreground /
 hard- / easy-background boxes with the reference's numpy / torch random draws (same seeds -> same samples), residual targets are
-encoded in each RoI's frame, and the RoI MLP is trained with the IoU-scaled BCE + masked L1 losses."""
+encoded in each RoI's frame, and the RoI MLP is trained with the IoU-scaled BCE + masked L1 losses.
+
+Device path (csrc/roi_head.hip; `pack_rois`, `roi_bev_features`, `match_rois_to_gt`, `roi_targets`, `refine_rois` below): everything
+between the first stage's predict and the RoI MLP, and behind the MLP at inference, in one launch each.  The neck map is read where it
+lies (NCHW or channels_last, fp32 or bf16): no fp32 NHWC copy.  Training reads `max_iou` back once (the sampling draws are the
+reference's host draws, `ProposalTargetLayer.subsample_rois_host`) and sends the sampled indices with their slot-to-row table in one
+copy; only the ROI_PER_IMAGE sampled RoIs get BEV features.  `TwoStageDetector.forward` takes this path whenever it applies
+(`TwoStageDetector.device_path_reason`), `S2D_ROI_DEVICE=0` keeps the torch chain; `det.roi_paths` counts the calls of each."""
+import ctypes
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import registry
+from . import _lib, registry
 from .registry import DETECTORS, ROI_HEAD, SECOND_STAGE
+
+ROI_MAX_GT = 512      # S2D_ROI_MAX_GT: ground-truth rows per sample that s2d_roi_match_gt stages in LDS
+ROI_MAX_BATCH = 64    # S2D_ROI_MAX_BATCH: the per-sample offsets of s2d_roi_pack travel in the kernel arguments
 
 
 def bilinear_interpolate(im, x, y):
@@ -109,6 +122,113 @@ def boxes_iou3d(boxes_a, boxes_b, bev_iou=None):
     return overlaps_3d / torch.clamp(vol_a + vol_b - overlaps_3d, min=1e-6)
 
 
+def _device_args(what, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise _lib.S2DError(f"{what}: CUDA tensors expected (no CPU fallback)")
+    dev = tensors[0].device
+    return _lib.load(), dev, torch._C._cuda_getCurrentRawStream(dev.index)
+
+
+def _f32c(t):
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def pack_rois(boxes, scores, labels, offsets, cap):
+    """the packed first-stage lists (boxes [total, 7 | 9] heading last, scores [total], labels [total] int64; sample b = rows
+    offsets[b] .. offsets[b + 1], host ints) as the zero-padded rois [B, cap, 7], roi_scores [B, cap], roi_labels [B, cap] = label + 1
+    of `reorder_first_stage_pred_and_feature`, in one launch and without a device read"""
+    lib, dev, st = _device_args("pack_rois", boxes, scores, labels)
+    bs = len(offsets) - 1
+    boxes, scores, labels = _f32c(boxes), _f32c(scores), labels.long().contiguous()
+    if int(offsets[-1]) != boxes.shape[0] or scores.shape[0] != boxes.shape[0] or labels.shape[0] != boxes.shape[0]:
+        raise _lib.S2DError(f"pack_rois: offsets end at {offsets[-1]}, lists hold {boxes.shape[0]} / {scores.shape[0]} / {labels.shape[0]} rows")
+    rois = torch.empty((bs, cap, 7), dtype=torch.float32, device=dev)
+    roi_scores = torch.empty((bs, cap), dtype=torch.float32, device=dev)
+    roi_labels = torch.empty((bs, cap), dtype=torch.int64, device=dev)
+    off = (ctypes.c_int32 * (bs + 1))(*[int(o) for o in offsets])
+    _lib.check(lib.s2d_roi_pack(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), boxes.shape[1] if boxes.dim() == 2 else 7, off, bs, cap,
+                                rois.data_ptr(), roi_scores.data_ptr(), roi_labels.data_ptr(), st), "s2d_roi_pack")
+    return rois, roi_scores, roi_labels
+
+
+def roi_bev_features(bev, boxes, row, pc_start, voxel_size, out_stride, num_point=5):
+    """BEV features of the boxes named by `row` [B, cap] int32 (rows of the packed list `boxes` [total, 7 | 9], -1 = empty slot ->
+    zeros): [B, cap, num_point * C] fp32, the numbers of `box_side_centers` + `BEVFeatureExtractor`.  bev [B, C, H, W] fp32 or bf16 is
+    read in place with its own strides (NCHW and channels_last alike; channels_last takes 16-byte loads)."""
+    lib, dev, st = _device_args("roi_bev_features", bev, boxes, row)
+    if bev.dtype not in (torch.float32, torch.bfloat16):
+        bev = bev.float()
+    boxes = _f32c(boxes)
+    row = row.int().contiguous()
+    bs, c, h, w = bev.shape
+    if row.dim() != 2 or row.shape[0] != bs:
+        raise _lib.S2DError(f"roi_bev_features: row table {tuple(row.shape)} for a map of {bs} samples")
+    feats = torch.empty((bs, row.shape[1], num_point * c), dtype=torch.float32, device=dev)
+    _lib.check(lib.s2d_roi_bev_features(bev.data_ptr(), int(bev.dtype == torch.bfloat16), bs, c, h, w, *bev.stride(), boxes.data_ptr(), boxes.shape[0],
+                                        boxes.shape[1] if boxes.dim() == 2 else 7, row.data_ptr(), row.shape[1], int(num_point), float(pc_start[0]),
+                                        float(pc_start[1]), float(voxel_size[0]), float(voxel_size[1]), float(out_stride), feats.data_ptr(), st),
+               "s2d_roi_bev_features")
+    return feats
+
+
+def match_rois_to_gt(rois, roi_labels, gt, by_class=True):
+    """every RoI's best 3-D IoU with its sample's valid ground truth and that row: (max_iou [B, cap] fp32, assignment [B, cap] int64,
+    gt_count [B] int32).  rois [B, cap, 7], roi_labels [B, cap], gt [B, G, >= 8] (box in the first 7 columns, class last; G <=
+    ROI_MAX_GT).  What `ProposalTargetLayer.sample_rois_for_rcnn` computes per sample before the sampling, for all samples in one launch."""
+    lib, dev, st = _device_args("match_rois_to_gt", rois, roi_labels, gt)
+    rois, gt, roi_labels = _f32c(rois), _f32c(gt), roi_labels.long().contiguous()
+    bs, cap = roi_labels.shape
+    max_iou = torch.empty((bs, cap), dtype=torch.float32, device=dev)
+    assignment = torch.empty((bs, cap), dtype=torch.int64, device=dev)
+    gt_count = torch.empty((bs,), dtype=torch.int32, device=dev)
+    _lib.check(lib.s2d_roi_match_gt(rois.data_ptr(), roi_labels.data_ptr(), bs, cap, gt.data_ptr(), gt.shape[1], gt.shape[2], int(bool(by_class)),
+                                    max_iou.data_ptr(), assignment.data_ptr(), gt_count.data_ptr(), st), "s2d_roi_match_gt")
+    return max_iou, assignment, gt_count
+
+
+def roi_targets(idx, rois, roi_labels, roi_scores, max_iou, assignment, gt, sampler_cfg):
+    """`ProposalTargetLayer.forward` behind the sampling + `RoIHead.assign_targets` for the sampled slots idx [B, per] (int32): the dict
+    of rois, roi_labels, roi_scores, gt_iou_of_rois, gt_of_rois_src, gt_of_rois (encoded), reg_valid_mask, rcnn_cls_labels"""
+    lib, dev, st = _device_args("roi_targets", idx, rois, roi_labels, roi_scores, max_iou, assignment, gt)
+    kind = _cfg_get(sampler_cfg, "CLS_SCORE_TYPE")
+    if kind not in ("cls", "roi_iou"):
+        raise NotImplementedError(kind)
+    idx = idx.int().contiguous()
+    rois, roi_scores, max_iou, gt = _f32c(rois), _f32c(roi_scores), _f32c(max_iou), _f32c(gt)
+    roi_labels, assignment = roi_labels.long().contiguous(), assignment.long().contiguous()
+    bs, per = idx.shape
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    l = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
+    out = dict(rois=f(bs, per, rois.shape[-1]), roi_labels=l(bs, per), roi_scores=f(bs, per), gt_iou_of_rois=f(bs, per), gt_of_rois_src=f(bs, per, 8),
+               gt_of_rois=f(bs, per, 8), reg_valid_mask=l(bs, per), rcnn_cls_labels=f(bs, per) if kind == "roi_iou" else l(bs, per))
+    _lib.check(lib.s2d_roi_targets(idx.data_ptr(), bs, per, rois.shape[1], rois.shape[-1], rois.data_ptr(), roi_labels.data_ptr(), roi_scores.data_ptr(),
+                                   max_iou.data_ptr(), assignment.data_ptr(), gt.data_ptr(), gt.shape[1], gt.shape[2],
+                                   float(_cfg_get(sampler_cfg, "REG_FG_THRESH")), float(_cfg_get(sampler_cfg, "CLS_FG_THRESH")),
+                                   float(_cfg_get(sampler_cfg, "CLS_BG_THRESH")), int(kind == "roi_iou"), out["rois"].data_ptr(),
+                                   out["roi_labels"].data_ptr(), out["roi_scores"].data_ptr(), out["gt_iou_of_rois"].data_ptr(),
+                                   out["gt_of_rois_src"].data_ptr(), out["gt_of_rois"].data_ptr(), out["reg_valid_mask"].data_ptr(),
+                                   out["rcnn_cls_labels"].data_ptr(), st), "s2d_roi_targets")
+    return out
+
+
+def refine_rois(rois, roi_scores, roi_labels, rcnn_cls, rcnn_reg):
+    """`RoIHead.generate_predicted_boxes` + the arithmetic of `TwoStageDetector.post_process`: (boxes [B, cap, 7], scores [B, cap] =
+    sqrt(sigmoid(cls) * roi_score), labels [B, cap] = roi_label - 1).  The caller slices every sample to its first count_b slots."""
+    lib, dev, st = _device_args("refine_rois", rois, roi_scores, roi_labels, rcnn_cls, rcnn_reg)
+    bs, cap = roi_labels.shape
+    rois, roi_scores, roi_labels = _f32c(rois), _f32c(roi_scores), roi_labels.long().contiguous()
+    rcnn_cls, rcnn_reg = _f32c(rcnn_cls.detach()), _f32c(rcnn_reg.detach())
+    if rois.shape[-1] != 7 or rcnn_reg.numel() != bs * cap * 7 or rcnn_cls.numel() != bs * cap:
+        raise _lib.S2DError(f"refine_rois: rois {tuple(rois.shape)}, rcnn_cls {tuple(rcnn_cls.shape)}, rcnn_reg {tuple(rcnn_reg.shape)} (code size 7, one class)")
+    boxes = torch.empty((bs, cap, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((bs, cap), dtype=torch.float32, device=dev)
+    labels = torch.empty((bs, cap), dtype=torch.int64, device=dev)
+    _lib.check(lib.s2d_roi_refine(rois.data_ptr(), roi_scores.data_ptr(), roi_labels.data_ptr(), rcnn_cls.data_ptr(), rcnn_reg.data_ptr(), bs * cap,
+                                  boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), st), "s2d_roi_refine")
+    return boxes, scores, labels
+
+
 class ProposalTargetLayer(nn.Module):
     """IoU-based sampling of the first stage's RoIs and their classification / regression labels
     (proposal_target_layer.py).  The random draws are the reference's (np.random.permutation / np.random.rand on the host,
@@ -189,6 +309,48 @@ class ProposalTargetLayer(nn.Module):
         else:
             raise NotImplementedError(f"ProposalTargetLayer: no RoI to sample (max IoU in [{float(max_overlaps.min())}, {float(max_overlaps.max())}])")
         return torch.cat((fg, bg), dim=0)
+
+    def subsample_rois_host(self, max_overlaps):
+        """`subsample_rois` + `sample_bg_inds` on a host array [n] (fp32): the SAME draws in the same order (np.random.permutation,
+        np.random.rand, torch.randint on the CPU generator), so a seeded run samples the RoIs the torch chain samples.  Returns int64
+        indices [ROI_PER_IMAGE] (numpy)."""
+        mo = np.asarray(max_overlaps, dtype=np.float32)
+        f = np.float32   # python scalars meet an fp32 tensor as their fp32 rounding
+        per = self._c("ROI_PER_IMAGE")
+        fg_per = int(np.round(self._c("FG_RATIO") * per))
+        fg_thresh = min(self._c("REG_FG_THRESH"), self._c("CLS_FG_THRESH"))
+        fg = np.nonzero(mo >= f(fg_thresh))[0]
+        easy = np.nonzero(mo < f(self._c("CLS_BG_THRESH_LO")))[0]
+        hard = np.nonzero((mo < f(self._c("REG_FG_THRESH"))) & (mo >= f(self._c("CLS_BG_THRESH_LO"))))[0]
+
+        def draw(n, k):
+            return torch.randint(low=0, high=n, size=(k,)).long().numpy()
+
+        def sample_bg(count):
+            ratio = self._c("HARD_BG_RATIO")
+            if len(hard) > 0 and len(easy) > 0:
+                n_hard = min(int(count * ratio), len(hard))
+                h = hard[draw(len(hard), n_hard)]
+                return np.concatenate([h, easy[draw(len(easy), count - n_hard)]])
+            if len(hard) > 0:
+                return hard[draw(len(hard), count)]
+            if len(easy) > 0:
+                return easy[draw(len(easy), count)]
+            raise NotImplementedError
+
+        n_fg, n_bg = len(fg), len(hard) + len(easy)
+        bg = fg[:0]
+        if n_fg > 0 and n_bg > 0:
+            take = min(fg_per, n_fg)
+            fg = fg[np.random.permutation(n_fg)[:take]]
+            bg = sample_bg(per - take)
+        elif n_fg > 0:
+            fg = fg[np.floor(np.random.rand(per) * n_fg).astype(np.int64)]
+        elif n_bg > 0:
+            fg, bg = fg[:0], sample_bg(per)
+        else:
+            raise NotImplementedError(f"ProposalTargetLayer: no RoI to sample (max IoU in [{float(mo.min())}, {float(mo.max())}])")
+        return np.concatenate([fg, bg]).astype(np.int64)
 
     @staticmethod
     def sample_bg_inds(hard, easy, count, hard_ratio):
@@ -336,11 +498,41 @@ class RoIHead(nn.Module):
         box[:, 0:3] += xyz
         return batch_cls, box.view(batch_size, -1, code_size)
 
-    def forward(self, batch_dict, training=True):
+    def assign_targets_device(self, batch_dict):
+        """`assign_targets` on the device kernels: IoU match of all samples in one launch, ONE device-to-host copy (max_iou), the
+        reference's host draws (`subsample_rois_host`), ONE host-to-device copy (the sampled slots and their rows in the packed box
+        list), then the gather + encode launch.  The BEV features are computed for the sampled RoIs only when the caller supplies
+        `roi_feature_fn(row)` with `roi_offsets` (TwoStageDetector), or gathered from `roi_features`.  Same keys, shapes and dtypes
+        as `assign_targets`."""
+        ptl = self.proposal_target_layer
+        if ptl is None:
+            raise ValueError("RoIHead: model_cfg.TARGET_CONFIG is required for training")
+        rois, labels, scores, gt = batch_dict["rois"], batch_dict["roi_labels"], batch_dict["roi_scores"], batch_dict["gt_boxes_and_cls"]
+        bs, cap = labels.shape
+        with torch.no_grad():
+            max_iou, assignment, _ = match_rois_to_gt(rois, labels, gt, by_class=ptl._c("SAMPLE_ROI_BY_EACH_CLASS", False))
+            host_iou = max_iou.cpu().numpy()                                   # the device-to-host copy
+            idx = np.stack([ptl.subsample_rois_host(host_iou[b]) for b in range(bs)])
+            table = np.zeros((2, bs, idx.shape[1]), np.int32)
+            table[0] = idx
+            offsets = batch_dict.get("roi_offsets")
+            if offsets is not None:   # slot -> row of the packed box list; the zero padding behind a sample's RoIs has no row
+                off = np.asarray(offsets, np.int64)
+                table[1] = np.where(idx < np.minimum(off[1:] - off[:-1], cap)[:, None], idx + off[:-1, None], -1)
+            table = torch.from_numpy(table).to(rois.device)                    # the host-to-device copy
+            t = roi_targets(table[0], rois, labels, scores, max_iou, assignment, gt, ptl.cfg)
+            if "roi_feature_fn" in batch_dict:
+                t["roi_features"] = batch_dict["roi_feature_fn"](table[1])
+            else:
+                t["roi_features"] = batch_dict["roi_features"][torch.arange(bs, device=rois.device)[:, None], table[0].long()]
+        return t
+
+    def forward(self, batch_dict, training=True, device=False):
+        """device=True: targets (training) and refinement (inference) on the kernels of csrc/roi_head.hip - CUDA tensors, code size 7"""
         batch_dict["batch_size"] = len(batch_dict["rois"])
         targets = None
         if training:   # roi_head.py:76-80
-            targets = self.assign_targets(batch_dict)
+            targets = self.assign_targets_device(batch_dict) if device else self.assign_targets(batch_dict)
             batch_dict["rois"], batch_dict["roi_labels"], batch_dict["roi_features"] = targets["rois"], targets["roi_labels"], targets["roi_features"]
         pooled = batch_dict["roi_features"].reshape(-1, 1, batch_dict["roi_features"].shape[-1]).permute(0, 2, 1).contiguous()
         shared = self.shared_fc_layer(pooled)
@@ -349,6 +541,11 @@ class RoIHead(nn.Module):
         if training:
             targets["rcnn_cls"], targets["rcnn_reg"] = rcnn_cls, rcnn_reg
             self.forward_ret_dict = targets
+            return batch_dict
+        if device:
+            box, scores, labels = refine_rois(batch_dict["rois"], batch_dict["roi_scores"], batch_dict["roi_labels"], rcnn_cls, rcnn_reg)
+            batch_dict["batch_cls_preds"], batch_dict["batch_box_preds"] = rcnn_cls.view(batch_dict["batch_size"], -1, rcnn_cls.shape[-1]), box
+            batch_dict["refined_scores"], batch_dict["refined_labels"], batch_dict["cls_preds_normalized"] = scores, labels, False
             return batch_dict
         cls, box = self.generate_predicted_boxes(batch_dict["batch_size"], batch_dict["rois"], rcnn_cls, rcnn_reg)
         batch_dict["batch_cls_preds"], batch_dict["batch_box_preds"], batch_dict["cls_preds_normalized"] = cls, box, False
@@ -387,6 +584,7 @@ class TwoStageDetector(nn.Module):
         self.second_stage = nn.ModuleList([registry.build(m, SECOND_STAGE) for m in second_stage_modules])
         self.roi_head = registry.build(roi_head, ROI_HEAD)
         self.num_point = num_point
+        self.roi_paths = {"device": 0, "torch": 0}   # calls of forward() by the path their second stage took
 
     def train(self, mode=True):
         super().train(mode)
@@ -447,6 +645,89 @@ class TwoStageDetector(nn.Module):
             one_stage_loss["roi_cls_loss"].append(tb_dict["rcnn_loss_cls"])
         return one_stage_loss
 
+    def device_path_reason(self, one_stage_pred, bev_feature, example, return_loss):
+        """None when the second stage can run on the kernels of csrc/roi_head.hip, else why it takes the torch chain"""
+        if os.environ.get("S2D_ROI_DEVICE") == "0":
+            return "S2D_ROI_DEVICE=0"
+        if not (torch.is_tensor(bev_feature) and bev_feature.is_cuda and bev_feature.dim() == 4):
+            return "the neck map is not a CUDA tensor"
+        if bev_feature.dtype not in (torch.float32, torch.bfloat16):
+            return f"neck map dtype {bev_feature.dtype}"
+        if bev_feature.requires_grad and torch.is_grad_enabled():
+            return "the neck map carries a gradient (no backward through the BEV sampling)"
+        if self.roi_head.code_size != 7 or self.roi_head.num_class != 1:
+            return "code size 7 and one RoI class only"
+        if self.num_point not in (1, 5):
+            return f"num_point {self.num_point}"
+        if len(self.second_stage) != 1 or type(self.second_stage[0]) is not BEVFeatureExtractor:
+            return "second-stage modules other than one BEVFeatureExtractor"
+        if not 1 <= len(one_stage_pred) <= ROI_MAX_BATCH or len(one_stage_pred) != bev_feature.shape[0]:
+            return f"{len(one_stage_pred)} samples"
+        for p in one_stage_pred:
+            b = p["box3d_lidar"]
+            if not b.is_cuda or b.dim() != 2 or b.shape[1] != 7 or b.shape[0] > self.NMS_POST_MAXSIZE:
+                return f"first-stage boxes {tuple(b.shape)}"
+        if return_loss:
+            gt = example.get("gt_boxes_and_cls")
+            ptl = self.roi_head.proposal_target_layer
+            if ptl is None or ptl.iou_fn is not boxes_iou3d or ptl._c("CLS_SCORE_TYPE") not in ("cls", "roi_iou"):
+                return "no or a custom proposal target layer"
+            if not (torch.is_tensor(gt) and gt.is_cuda and gt.dim() == 3 and gt.shape[2] >= 8 and 1 <= gt.shape[1] <= ROI_MAX_GT):
+                return f"ground truth outside the match kernel's bound ({ROI_MAX_GT} rows per sample)"
+        return None
+
+    @staticmethod
+    def _packed_first_stage(preds):
+        """(boxes, scores, labels, offsets) of the whole batch.  CenterHead.predict's device path hands out per-sample views of one packed
+        tensor each: those are taken as they are, anything else is concatenated."""
+        counts = [int(p["box3d_lidar"].shape[0]) for p in preds]
+        offsets = [0]
+        for c in counts:
+            offsets.append(offsets[-1] + c)
+
+        def packed(key):
+            parts = [p[key] for p in preds]
+            base = parts[0]._base
+            if base is not None and base.is_contiguous() and base.shape[0] == offsets[-1] and base.shape[1:] == parts[0].shape[1:]:
+                row = base[0].numel() if base.shape[0] else 1
+                if all(q._base is base and q.is_contiguous() and q.storage_offset() == base.storage_offset() + o * row for q, o in zip(parts, offsets)):
+                    return base
+            return torch.cat(parts, dim=0)
+        return packed("box3d_lidar"), packed("scores"), packed("label_preds"), offsets
+
+    def _forward_device(self, one_stage_pred, bev_feature, example, return_loss):
+        """the second stage on the device kernels: pack -> (match -> host sampling -> targets) -> BEV features of the RoIs the MLP
+        will see -> RoI MLP -> (refine).  `example` gets the RoI tensors the chain puts there; the fp32 NHWC copy of the neck map
+        (`example["bev_feature"]`) is NOT made - the map is sampled where it lies."""
+        boxes, scores, labels, offsets = self._packed_first_stage(one_stage_pred)
+        bs, cap, ext = len(one_stage_pred), self.NMS_POST_MAXSIZE, self.second_stage[0]
+        bev = bev_feature.detach()
+        rois, roi_scores, roi_labels = pack_rois(boxes, scores, labels, offsets, cap)
+        feature_fn = lambda row: roi_bev_features(bev, boxes, row, ext.pc_start, ext.voxel_size, ext.out_stride, self.num_point)
+        example.update(rois=rois, roi_labels=roi_labels, roi_scores=roi_scores, has_class_labels=True)
+        if return_loss:
+            example["gt_boxes_and_cls"] = example["gt_boxes_and_cls"][:, :, [0, 1, 2, 3, 4, 5, 6, -1]]   # two_stage.py:173-175
+            example.update(roi_feature_fn=feature_fn, roi_offsets=offsets)
+            try:
+                self.roi_head(example, training=True, device=True)
+            finally:
+                del example["roi_feature_fn"], example["roi_offsets"]
+            return None
+        row = np.full((bs, cap), -1, np.int32)
+        for b in range(bs):
+            n = offsets[b + 1] - offsets[b]
+            row[b, :n] = np.arange(offsets[b], offsets[b + 1], dtype=np.int32)
+        with torch.no_grad():
+            example["roi_features"] = feature_fn(torch.from_numpy(row).to(rois.device))
+        batch_dict = self.roi_head(example, training=False, device=True)
+        meta = batch_dict.get("metadata")
+        out = []
+        for b in range(bs):   # the valid RoIs of a sample are its first slots: the host slices, no mask and no read
+            n = offsets[b + 1] - offsets[b]
+            out.append(dict(box3d_lidar=batch_dict["batch_box_preds"][b, :n], scores=batch_dict["refined_scores"][b, :n],
+                            label_preds=batch_dict["refined_labels"][b, :n], metadata=meta[b] if meta else None))
+        return out
+
     def forward(self, example, return_loss=True, return_feature=False, **kwargs):
         out = self.single_det.forward_two_stage(example, return_loss, **kwargs)
         f_a = f_b = None
@@ -455,6 +736,14 @@ class TwoStageDetector(nn.Module):
         else:
             one_stage_pred, bev_feature, voxel_feature, one_stage_loss = out
         example["voxel_feature"] = voxel_feature
+        if self.device_path_reason(one_stage_pred, bev_feature, example, return_loss) is None:
+            self.roi_paths["device"] += 1
+            res = self._forward_device(one_stage_pred, bev_feature, example, return_loss)
+            if return_loss:
+                roi_loss, tb = self.roi_head.get_loss()
+                return self.combine_loss(one_stage_loss, roi_loss, tb)
+            return (res, f_a, f_b) if return_feature else res
+        self.roi_paths["torch"] += 1
         example["bev_feature"] = bev_feature.float().permute(0, 2, 3, 1).contiguous()   # N C H W -> N H W C
         centers = self.get_box_center(one_stage_pred)
         if self.roi_head.code_size == 7 and return_loss:   # drop the velocity columns (two_stage.py:173-175)

@@ -7,6 +7,7 @@ det3d_shim.Config.fromfile; these literals exist so that bench.py and the GPU te
   s2d_student()            same file :48-76 (`S_model`)
   second_voxelnet_parts()  configs/waymo/voxelnet/waymo_second_3x_interval_5.py (reader/backbone/neck of config 1)
   second_voxelnet_train()  same file :58-106 with the full head dictionaries (:78-105); SECOND_ASSIGNER :15-55,108-113; SECOND_TEST_CFG :117-130
+  two_stage_voxelnet()     configs/waymo/voxelnet/two_stage/waymo_centerpoint_voxelnet_two_stage_distill.py:19-101 (`S_model`; BASELINE configs 3, 5)
   nusc_centerpoint_dcn()   configs/nusc/voxelnet/nusc_centerpoint_voxelnet_0075voxel_dcn.py:6-13,23-55 (`model`: CenterHead with dcn_head=True)
 """
 import logging
@@ -38,6 +39,27 @@ def s2d_student():
                 reader=dict(type="VoxelFeatureExtractorV3", num_input_features=5),
                 backbone=dict(type="SpMiddleResNetFHD", num_input_features=5, ds_factor=8),
                 neck=_neck("S2D_RPN"), bbox_head=_head())
+
+
+def two_stage_voxelnet():
+    """the two-stage student: frozen KD_VoxelNet first stage (`pretrained` left empty: no checkpoint travels with the repository),
+    five BEV sample points per box, the RoI MLP with its IoU-guided targets"""
+    sampler = dict(ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE="roi_iou", CLS_FG_THRESH=0.75,
+                   CLS_BG_THRESH=0.25, CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55)
+    loss = dict(CLS_LOSS="BinaryCrossEntropy", REG_LOSS="L1",
+                LOSS_WEIGHTS={"rcnn_cls_weight": 1.0, "rcnn_reg_weight": 1.0, "code_weights": [1.0] * 7})
+    return dict(type="TwoStageDetector", first_stage_cfg=s2d_student(),
+                second_stage_modules=[dict(type="BEVFeatureExtractor", pc_start=[-75.2, -75.2], voxel_size=[0.1, 0.1], out_stride=8)],
+                roi_head=dict(type="RoIHead", input_channels=512 * 5, code_size=7,
+                              model_cfg=dict(CLASS_AGNOSTIC=True, SHARED_FC=[256, 256], CLS_FC=[256, 256], REG_FC=[256, 256], DP_RATIO=0.3,
+                                             TARGET_CONFIG=sampler, LOSS_CONFIG=loss)),
+                NMS_POST_MAXSIZE=500, num_point=5, freeze=True)
+
+
+TWO_STAGE_TEST_CFG = dict(post_center_limit_range=[-80, -80, -10.0, 80, 80, 10.0], max_per_img=4096, score_threshold=0.1, pc_range=[-75.2, -75.2],
+                          out_size_factor=8, voxel_size=[0.1, 0.1],
+                          nms=dict(use_rotate_nms=True, use_multi_class_nms=False, nms_pre_max_size=4096, nms_post_max_size=500,
+                                   nms_iou_threshold=0.7))
 
 
 def second_voxelnet():
