@@ -939,6 +939,50 @@ int s2d_anchor_decode(const float *box_preds, const float *cls_preds, const floa
                       int32_t *dir_labels, uint8_t *keep, s2d_stream_t stream);
 
 /*
+ * MultiGroupHead.predict on the device for ALL tasks and samples of a head at once (csrc/anchor_predict.hip; mg_head.py:697-1086,
+ * single-class rotated-NMS branch).  A SEGMENT is one (task, sample) pair, segment = task * samples + sample.  One record per task, passed
+ * as a HOST array of 1..8 entries (it travels in the kernel arguments): the contiguous fp32 head outputs box_preds [samples][num_anchors][7],
+ * cls_preds [samples][num_anchors][classes], dir_cls_preds [samples][num_anchors][2] (NULL: no direction classifier, direction label 0) and
+ * the anchor table [num_anchors][7].  max_anchors >= every task's num_anchors is the row length of the score maps.
+ *
+ * s2d_anchor_predict_score: score [segments][max_anchors] = the class maximum of sigmoid(cls_preds) (the expression of s2d_anchor_decode)
+ * where it is >= score_threshold, else -1 (a NaN maximum and the columns past the task's num_anchors included); label
+ * [segments][max_anchors] = its class (lowest index on a tie); count [segments] = passing anchors.
+ *
+ * s2d_anchor_predict_boxes: with order / score_sorted [segments][max_anchors] the descending stable sort of `score` along its last axis,
+ * rank r < min(counts[s], max_count) of segment s becomes row offsets[s] + r of the packed lists: boxes [total][7] = second_box_decode
+ * in the form the rotated NMS takes, (x, y, z, w, l, h, -r) (the arithmetic of s2d_anchor_decode, bit for bit); scores [total]; labels
+ * [total] (class inside the task); dir_labels [total] = argmax(dir_cls_preds); in_range [total] = 1 when the centre (x, y, z) lies inside
+ * range6 (HOST, xmin ymin zmin xmax ymax zmax, inclusive; NULL = every row is inside).  offsets / counts: DEVICE int32 [segments]; rows
+ * outside [0, total) are not written.
+ *
+ * s2d_anchor_predict_finish: after s2d_nms_rotated_bev_batched on those rows (keep [segments][max_keep], n_keep [segments], both on the
+ * DEVICE), one workgroup per segment walks the first min(n_keep[s], max_keep) kept rows in order, drops those whose in_range flag is
+ * clear, and writes out_boxes [segments][max_keep][7] = (x, y, z, w, l, h, r) with r + pi (fp32 pi) where use_direction and
+ * ((r - direction_offset) > 0) != (dir_label != 0) (mg_head.py:1057-1066), out_scores [segments][max_keep], out_labels
+ * [segments][max_keep] (int64, class + the task's label_base; of the task records only label_base is read) and out_count [segments] -
+ * written for EVERY segment; entries past out_count[s] are left untouched.
+ */
+#define S2D_ANCHOR_PREDICT_MAX_TASKS 8
+typedef struct s2d_anchor_predict_task {
+    const float *box_preds, *cls_preds, *dir_cls_preds, *anchors;
+    int64_t num_anchors;
+    int classes;
+    int label_base;   /* added to the labels of the task by s2d_anchor_predict_finish */
+} s2d_anchor_predict_task;
+int s2d_anchor_predict_score(const s2d_anchor_predict_task *tasks, int num_tasks, int samples, int64_t max_anchors,
+                             float score_threshold, float *score, int32_t *label, int32_t *count, s2d_stream_t stream);
+int s2d_anchor_predict_boxes(const s2d_anchor_predict_task *tasks, int num_tasks, int samples, int64_t max_anchors,
+                             const float *range6, const int64_t *order, const float *score_sorted, const int32_t *label,
+                             const int32_t *offsets, const int32_t *counts, int max_count, int64_t total, float *boxes, float *scores,
+                             int32_t *labels, int32_t *dir_labels, uint8_t *in_range, s2d_stream_t stream);
+int s2d_anchor_predict_finish(const s2d_anchor_predict_task *tasks, int num_tasks, int samples, const float *boxes, const float *scores,
+                              const int32_t *labels, const int32_t *dir_labels, const uint8_t *in_range, const int32_t *offsets,
+                              const int32_t *counts, int64_t total, const int64_t *keep, const int32_t *n_keep, int max_keep,
+                              int use_direction, float direction_offset, float *out_boxes, float *out_scores,
+                              int64_t *out_labels, int32_t *out_count, s2d_stream_t stream);
+
+/*
  * Optimizer step of the reference's training loop (det3d/torchie/apis/train.py:168-186, det3d/solver/fastai_optim.py:158-171,
  * hooks/optimizer.py:15-21): gradient L2 norm -> clip coefficient (device scalar, clip_grad_norm_ semantics) -> fused
  * multi-tensor Adam with decoupled weight decay: p *= 1 - lr*wd; Adam(betas, eps) on grad*clip_coef with bias correction of

@@ -28,6 +28,12 @@ class CenterPredictTask(ctypes.Structure):
                 ("classes", ctypes.c_int), ("label_base", ctypes.c_int)]
 
 
+class AnchorPredictTask(ctypes.Structure):
+    """s2d_anchor_predict_task of include/s2d.h: the head outputs and the anchor table of one MultiGroupHead task"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("box_preds", "cls_preds", "dir_cls_preds", "anchors")] + \
+               [("num_anchors", ctypes.c_int64), ("classes", ctypes.c_int), ("label_base", ctypes.c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/s2d.h one to one
 SIGNATURES = {
     "s2d_version": (ctypes.c_int, []),
@@ -408,6 +414,12 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_float), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "s2d_anchor_decode": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_float, c_f32p,
                                          c_f32p, c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_void_p]),
+    # MultiGroupHead.predict on the device (csrc/anchor_predict.hip)
+    "s2d_anchor_predict_score": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_float] + [ctypes.c_void_p] * 4),
+    "s2d_anchor_predict_boxes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 6 +
+                                 [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 6),
+    "s2d_anchor_predict_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int64] +
+                                  [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 5),
     # deformable convolution v1 (csrc/deform_conv.hip)
     "s2d_deform_conv_supported": (ctypes.c_int, [ctypes.c_int] * 9),
     "s2d_deform_conv_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),

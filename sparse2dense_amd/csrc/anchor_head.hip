@@ -12,7 +12,7 @@
 // Anchor a of a frame sits in slot a % (classes * rotations) of its cell; slots [c * rotations, (c + 1) * rotations) belong to class c
 // (generate_anchors concatenates the classes along the slot axis, target_assigner.py:139-158).
 // Sums are per-block slabs folded in a fixed order (no float atomics): every result is bitwise reproducible run to run.
-#include "s2d_common.h"
+#include "anchor_decode.h"
 
 namespace s2d {
 
@@ -315,26 +315,9 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float *__restr
     const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (at >= total) return;
     const float *an = anchors + (at % num_anchors) * 7, *t = box_preds + at * 7;
-    float best = 0.f;
-    int arg = 0;
-    for (int j = 0; j < classes; ++j) {
-        const float x = cls_preds[at * classes + j];
-        const float e = expf(-fabsf(x));
-        const float p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-        if (j == 0 || p > best) {
-            best = p;
-            arg = j;
-        }
-    }
-    const float diagonal = sqrtf(an[4] * an[4] + an[3] * an[3]);
-    float *o = boxes + at * 7;
-    o[0] = t[0] * diagonal + an[0];
-    o[1] = t[1] * diagonal + an[1];
-    o[2] = t[2] * an[5] + an[2];
-    o[3] = expf(t[3]) * an[3];
-    o[4] = expf(t[4]) * an[4];
-    o[5] = expf(t[5]) * an[5];
-    o[6] = t[6] + an[6];
+    int arg;
+    const float best = anchor_class_max(cls_preds + at * classes, classes, arg);
+    anchor_box_decode(t, an, boxes + at * 7);
     scores[at] = best;
     labels[at] = arg;
     dir_labels[at] = dir_preds ? (dir_preds[at * 2 + 1] > dir_preds[at * 2] ? 1 : 0) : 0;

@@ -8,7 +8,8 @@
   mask_offset_loss                 /root/reference/det3d/models/detectors/voxelnet.py:171-185
 
 `CenterHead.predict` (decode + rotated / circle NMS) runs on the device through center_predict.py for CUDA
-maps; `CenterHead.predict_torch` is the per-segment torch chain it replaced.
+maps; `CenterHead.predict_torch` is the per-segment torch chain it replaced.  `MultiGroupHead.predict` likewise through
+anchor_predict.py, with `MultiGroupHead.predict_torch` as the chain.
 """
 import copy
 import ctypes
@@ -1076,8 +1077,8 @@ class MultiGroupHead(nn.Module):
     """Constructor signature and parameter names of the reference head
     (/root/reference/det3d/models/bbox_heads/mg_head.py:386-533).  `loss` and `predict` cover the Waymo SECOND configuration (3d mode,
     ground_box3d_coder, NormByNumPositives, SigmoidFocalLoss, codewise WeightedSmoothL1Loss, softmax direction classifier, sin-difference
-    angle coding, rotated single-class NMS) through the kernels of csrc/anchor_head.hip (sparse2dense_amd/anchors.py); any other
-    combination raises NotImplementedError naming the option."""
+    angle coding, rotated single-class NMS) through the kernels of csrc/anchor_head.hip (sparse2dense_amd/anchors.py) and, for `predict`,
+    of csrc/anchor_predict.hip (sparse2dense_amd/anchor_predict.py); any other combination raises NotImplementedError naming the option."""
 
     graph_segment = False   # detectors._dense_call: neck + this head (+ loss) are not replayed as HIP graphs (eager launches)
 
@@ -1108,6 +1109,7 @@ class MultiGroupHead(nn.Module):
         self.encode_rad_error_by_sin = encode_rad_error_by_sin
         self.loss_norm, self.loss_cls, self.loss_reg, self.loss_aux = loss_norm, loss_cls, loss_bbox, loss_aux
         self.bev_only = mode == "bev"
+        self.predict_paths = {"device": 0, "torch": 0}   # calls of predict() by the path they took
         self.tasks = nn.ModuleList()
         for num_c, num_a in zip(num_classes, self.num_anchor_per_locs):
             num_cls = num_a * num_c if encode_background_as_zeros else num_a * (num_c + 1)
@@ -1159,9 +1161,57 @@ class MultiGroupHead(nn.Module):
                 merged[k].append(v)
         return merged
 
+    @staticmethod
+    def _check_test_cfg(test_cfg):
+        """the test_cfg checks of `predict_torch`, made by `predict` in front of the device path as well (the same texts)"""
+        get = (lambda k, d=None: test_cfg.get(k, d)) if hasattr(test_cfg, "get") else (lambda k, d=None: getattr(test_cfg, k, d))
+        nms_cfg = get("nms")
+        nget = (lambda k, d=None: nms_cfg.get(k, d)) if isinstance(nms_cfg, dict) else (lambda k, d=None: getattr(nms_cfg, k, d))
+        if not nget("use_rotate_nms", False):
+            raise NotImplementedError("MultiGroupHead.predict: test_cfg.nms.use_rotate_nms=False is not supported")
+        if nget("use_multi_class_nms", False):
+            raise NotImplementedError("MultiGroupHead.predict: test_cfg.nms.use_multi_class_nms=True is not supported")
+        if not float(get("score_threshold")) > 0.0:
+            raise NotImplementedError("MultiGroupHead.predict: test_cfg.score_threshold <= 0 is not supported")
+
+    def device_predict_reason(self, preds_dicts):
+        """None when `predict` takes the device path (anchor_predict.py) for these predictions, else why it takes `predict_torch`"""
+        from . import anchor_predict
+        if os.environ.get("S2D_ANCHOR_DEVICE_PREDICT") == "0":
+            return "S2D_ANCHOR_DEVICE_PREDICT=0"
+        if len(preds_dicts) > anchor_predict.MAX_TASKS:
+            return f"more than {anchor_predict.MAX_TASKS} tasks"
+        if not preds_dicts:
+            return "no tasks"
+        if not all(torch.is_tensor(v) and v.is_cuda for p in preds_dicts for v in p.values()):
+            return "CPU tensors"
+        return None
+
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_cfg, **kwargs):
-        """mg_head.py:697-1086, single-class-NMS branch: decode + score threshold in one kernel (anchors.decode_anchors), candidates in
+        """mg_head.py:697-1086, single-class-NMS branch.  Returns one dict per sample: box3d_lidar [n, 7], scores [n], label_preds [n]
+        (int64), metadata.  CUDA predictions take the device path (anchor_predict.py: every task and sample in a handful of launches and
+        two host reads) whenever `device_predict_reason` gives none; S2D_ANCHOR_DEVICE_PREDICT=0, more than 8 tasks, or a segment above
+        the batched NMS kernels' bounds take `predict_torch`, which returns the same.  predict_paths counts the calls each took."""
+        from . import anchor_predict
+        self._check_supported("predict", example, kwargs)
+        self._check_test_cfg(test_cfg)
+        paths = self.predict_paths
+        if self.device_predict_reason(preds_dicts) is None:
+            per_sample = anchor_predict.predict_on_device(preds_dicts, [self._task_anchors(example, t) for t in range(len(preds_dicts))],
+                                                          test_cfg, self.num_classes, self.use_direction_classifier, self.direction_offset)
+            if per_sample is not None:   # (None: a segment above the NMS kernels' 65536 boxes, or their workspace above its bound)
+                paths["device"] += 1
+                meta = example.get("metadata") if isinstance(example, dict) else None
+                return [dict(box3d_lidar=b, scores=s, label_preds=l, metadata=meta[i] if meta else None)
+                        for i, (b, s, l) in enumerate(per_sample)]
+        paths["torch"] += 1
+        return self.predict_torch(example, preds_dicts, test_cfg, **kwargs)
+
+    @torch.no_grad()
+    def predict_torch(self, example, preds_dicts, test_cfg, **kwargs):
+        """the per-task, per-sample chain of `predict` (what it was before the device path, and what runs for CPU tensors, more than 8
+        tasks or S2D_ANCHOR_DEVICE_PREDICT=0): decode + score threshold in one kernel (anchors.decode_anchors), candidates in
         anchor order, top nms_pre_max_size by score, rotated NMS on the device, nms_post_max_size, direction flip, centre-range mask.
         The reference feeds rotate_nms_cc with (x, y, w, l, r) rectangles that turn clockwise for positive r (box_np_ops.py:207-220);
         the same rectangle in the (x, y, z, dx, dy, dz, heading) form of nms.rotate_nms is (dx, dy, heading) = (w, l, -r)."""

@@ -63,7 +63,7 @@ def circle_nms(centers_xy, scores, min_radius, post_max_size=83):
     return order[keep[:int(n_keep.item())]]
 
 
-def _nms_batched(entry, what, rows, segments, counts, thresh, post_max_size):
+def _nms_batched(entry, what, rows, segments, counts, thresh, post_max_size, n_keep_on_device=False):
     if not rows.is_cuda or not segments.is_cuda:
         raise _lib.S2DError(f"{what}: CUDA tensors expected (no CPU fallback)")
     lib = _lib.load()
@@ -77,23 +77,25 @@ def _nms_batched(entry, what, rows, segments, counts, thresh, post_max_size):
     keep = torch.empty((segs, max_keep), dtype=torch.int64, device=dev)
     n_keep = torch.empty((segs,), dtype=torch.int32, device=dev)
     if segs == 0:
-        return keep, []
+        return keep, (n_keep if n_keep_on_device else [])
     ws = torch.empty(lib.s2d_nms_batched_workspace_bytes(total, max_count), dtype=torch.uint8, device=dev)
     _lib.check(getattr(lib, entry)(rows.data_ptr(), rows.shape[1] if rows.dim() == 2 else 0, segments[0].data_ptr(), segments[1].data_ptr(), segs,
                                    max_count, total, thresh, max_keep, keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(),
                                    _stream(dev)), entry)
-    return keep, n_keep.tolist()
+    return keep, (n_keep if n_keep_on_device else n_keep.tolist())
 
 
-def rotate_nms_batched(boxes, segments, counts, thresh, post_max_size=None):
+def rotate_nms_batched(boxes, segments, counts, thresh, post_max_size=None, n_keep_on_device=False):
     """`rotate_nms` for many independent segments in two launches (s2d_nms_rotated_bev_batched): the per-(task, sample) loop of
     /root/reference/det3d/models/bbox_heads/center_head.py:455-481 over box_torch_ops.py:449-464.
     boxes: cuda fp32 [N, 7 or more] packed rows (x, y, z, dx, dy, dz, ..., heading LAST), each segment's rows contiguous and already sorted
     by descending score (a pre_maxsize cut is made by the caller: pass the rows that take part); segments: cuda int32 [2, S] = row
     offsets and row counts; counts: the same counts on the host (a list - they size the launch, each at most 65536).
     Returns (keep, n_keep): keep cuda int64 [S, max_keep] indices into each segment's own rows in descending-score order, of which the
-    first n_keep[s] (a host list: the one host read) are valid; max_keep = min(max(counts), post_max_size).  Current stream."""
-    return _nms_batched("s2d_nms_rotated_bev_batched", "rotate_nms_batched", boxes, segments, counts, float(thresh), post_max_size)
+    first n_keep[s] (a host list: the one host read) are valid; max_keep = min(max(counts), post_max_size).  With n_keep_on_device the
+    counts come back as the cuda int32 [S] tensor the kernel wrote and nothing is read on the host.  Current stream."""
+    return _nms_batched("s2d_nms_rotated_bev_batched", "rotate_nms_batched", boxes, segments, counts, float(thresh), post_max_size,
+                        n_keep_on_device)
 
 
 def circle_nms_batched(centers_xy, segments, counts, min_radius, post_max_size=83):
