@@ -2,9 +2,10 @@
  *   /root/reference/det3d/ops/iou3d_nms/src/iou3d_nms_kernel.cu:30-234 (box_overlap / iou_bev), :267-326 (nms_kernel),
  *   /root/reference/det3d/ops/iou3d_nms/src/iou3d_nms.cpp:92-130 (host walk of the suppression mask),
  *   /root/reference/det3d/core/bbox/box_torch_ops.py:449-464 (rotate_nms_pcdet: sort by score, pre/post max sizes).
- * PARITY UNPINNED BY REFERENCE-RUN VECTORS: the reference implementation is CUDA (its CPU twin iou3d_cpu.cpp includes <cuda.h>),
- * neither builds in this image.  The restatement is cross-checked against an independent float64 polygon-clipping IoU
- * (tests/test_nms.py).  Plain C, fp32 arithmetic in the reference's operation order. */
+ * PINNED: the reference's CPU twin of the geometry (det3d/ops/iou3d_nms/src/iou3d_cpu.cpp) is compiled by oracle/ref_iou3d.py, and
+ * tests/test_iou_pin.py holds s2d_oracle_bev_iou to what it returned for the degenerate families of tests/golden/iou_pairs.npz, bit
+ * for bit.  Also cross-checked against an independent float64 polygon-clipping IoU (tests/test_nms.py).  Plain C, fp32 arithmetic in
+ * the reference's operation order. */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
