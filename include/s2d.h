@@ -1209,6 +1209,49 @@ int s2d_roi_targets(const int32_t *idx, int batch, int per, int cap, int roi_dim
 int s2d_roi_refine(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *rcnn_cls, const float *rcnn_reg,
                    int64_t n, float *boxes, float *scores, int64_t *labels, s2d_stream_t stream);
 
+/*
+ * The eval-mode RoI MLP in one launch (csrc/roi_mlp.hip; roi_head.py:16-106, roi_head_template.py:27-41): feats [rows][cin] fp32
+ * row-major and 16-byte aligned (what s2d_roi_bev_features writes) -> rcnn_cls [rows][1], rcnn_reg [rows][7].  Every layer is
+ * y = act(scale[c] * (x . W^T)[c] + shift[c]) in exact fp32 on the matrix cores (v_mfma_f32_16x16x4_f32), scale and shift applied in the
+ * epilogue: Conv1d(k=1, no bias) + eval BatchNorm1d + ReLU has scale = gamma / sqrt(running_var + eps), shift = beta - running_mean *
+ * scale; the two final convolutions have scale 1, shift = bias and no ReLU; dropout is the identity.  No split-K, no atomics: a row's
+ * result depends on that row only and is the same bits whatever else is in the call.
+ *
+ * Shape family (s2d_roi_mlp_supported): cin % 4 == 0, cin <= 4096; n_shared 1 or 2 layers of widths s0, s1; n_cls and n_reg 0, 1 or 2
+ * hidden layers of widths c0, c1 / r0, r1; every hidden width a multiple of 16, at most 256 (widths behind a count are ignored);
+ * num_class 1, code_size 7.  Anything else is S2D_ERR_UNSUPPORTED - the caller keeps the torch MLP.
+ *
+ * s2d_roi_mlp_plan_make fills the layer table, which then travels BY VALUE in the kernel arguments: layers in the order shared .., cls
+ * hidden .., cls final, reg hidden .., reg final; cout_pad = cout for the hidden layers and 16 for the two final ones.
+ *   image:  packed[w_off + (ks * (cout_pad / 16) + t) * 64 + l] = W[16 t + (l & 15)][4 ks + (l >> 4)]  (W [cout][cin] row-major, zero
+ *           for rows past cout) - the B fragment of lane l for the 4-channel step ks and the 16-column tile t: one float per lane and
+ *           instruction, 256 contiguous bytes per wave.  packed_elems floats in all (s2d_roi_mlp_packed_elems).
+ *   affine: affine[affine_off + c] = scale[c], affine[affine_off + cout_pad + c] = shift[c], c < cout_pad (the padding is never read
+ *           into a result); affine_elems floats in all.  The caller writes it.
+ * s2d_roi_mlp_pack: one launch, weights = HOST array of num_layers device pointers in the table's order.
+ */
+#define S2D_ROI_MLP_MAX_LAYERS 8
+typedef struct s2d_roi_mlp_layer {
+    int32_t cin, cout, cout_pad, relu;
+    int32_t affine_off, reserved;
+    int64_t w_off;
+} s2d_roi_mlp_layer;
+typedef struct s2d_roi_mlp_plan {
+    int32_t num_layers, n_shared, n_cls, n_reg;
+    int64_t packed_elems;
+    int32_t affine_elems, reserved;
+    s2d_roi_mlp_layer layer[S2D_ROI_MLP_MAX_LAYERS];
+} s2d_roi_mlp_plan;
+int s2d_roi_mlp_supported(int cin, int n_shared, int s0, int s1, int n_cls, int c0, int c1, int n_reg, int r0, int r1, int num_class,
+                          int code_size);
+int64_t s2d_roi_mlp_packed_elems(int cin, int n_shared, int s0, int s1, int n_cls, int c0, int c1, int n_reg, int r0, int r1, int num_class,
+                                 int code_size);
+int s2d_roi_mlp_plan_make(int cin, int n_shared, int s0, int s1, int n_cls, int c0, int c1, int n_reg, int r0, int r1, int num_class,
+                          int code_size, s2d_roi_mlp_plan *plan);
+int s2d_roi_mlp_pack(const s2d_roi_mlp_plan *plan, const float *const *weights, float *packed, s2d_stream_t stream);
+int s2d_roi_mlp_run(const s2d_roi_mlp_plan *plan, const float *feats, int64_t rows, const float *packed, const float *affine, float *rcnn_cls,
+                    float *rcnn_reg, s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

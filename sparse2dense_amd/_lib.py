@@ -34,6 +34,17 @@ class AnchorPredictTask(ctypes.Structure):
                [("num_anchors", ctypes.c_int64), ("classes", ctypes.c_int), ("label_base", ctypes.c_int)]
 
 
+class RoiMlpLayer(ctypes.Structure):
+    """s2d_roi_mlp_layer of include/s2d.h"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("cin", "cout", "cout_pad", "relu", "affine_off", "reserved")] + [("w_off", ctypes.c_int64)]
+
+
+class RoiMlpPlan(ctypes.Structure):
+    """s2d_roi_mlp_plan of include/s2d.h: the layer table of the fused RoI MLP (filled by s2d_roi_mlp_plan_make)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_layers", "n_shared", "n_cls", "n_reg")] + [("packed_elems", ctypes.c_int64)] + \
+               [("affine_elems", ctypes.c_int32), ("reserved", ctypes.c_int32), ("layer", RoiMlpLayer * 8)]
+
+
 # name -> (restype, argtypes); mirrors include/s2d.h one to one
 SIGNATURES = {
     "s2d_version": (ctypes.c_int, []),
@@ -444,6 +455,12 @@ SIGNATURES = {
     "s2d_roi_targets": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int] +
                         [ctypes.c_double] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 9),
     "s2d_roi_refine": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    # the eval RoI MLP in one launch (csrc/roi_mlp.hip)
+    "s2d_roi_mlp_supported": (ctypes.c_int, [ctypes.c_int] * 12),
+    "s2d_roi_mlp_packed_elems": (ctypes.c_int64, [ctypes.c_int] * 12),
+    "s2d_roi_mlp_plan_make": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.POINTER(RoiMlpPlan)]),
+    "s2d_roi_mlp_pack": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_roi_mlp_run": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
 }
 
 _lib = None

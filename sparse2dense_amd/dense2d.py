@@ -93,7 +93,16 @@ def cached_pack_put(weight, variant, value):
     cached_pack(weight, variant, lambda: value)
 
 
+_pack_epoch = 0   # moved by clear_pack_cache() and refresh_pack_cache(): images cached elsewhere on the same keys (RoIHead's fused-MLP image) carry it in their key
+
+
+def pack_epoch():
+    return _pack_epoch
+
+
 def clear_pack_cache():
+    global _pack_epoch
+    _pack_epoch += 1
     _pack_cache.clear()
     _repack.clear()
     _repack_state.update(sig=None, graph=None, last=None, stable=0)
@@ -145,6 +154,8 @@ def _run_pack_launches(fns):
 
 def refresh_pack_cache():
     import os
+    global _pack_epoch
+    _pack_epoch += 1   # (images keyed on the epoch have no registered re-pack launch: rebuilt at their next use)
     mode = os.environ.get("S2D_PACK_GRAPH", "0")
     if mode == "off":
         return clear_pack_cache()

@@ -25,7 +25,11 @@ between the first stage's predict and the RoI MLP, and behind the MLP at inferen
 lies (NCHW or channels_last, fp32 or bf16): no fp32 NHWC copy.  Training reads `max_iou` back once (the sampling draws are the
 reference's host draws, `ProposalTargetLayer.subsample_rois_host`) and sends the sampled indices with their slot-to-row table in one
 copy; only the ROI_PER_IMAGE sampled RoIs get BEV features.  `TwoStageDetector.forward` takes this path whenever it applies
-(`TwoStageDetector.device_path_reason`), `S2D_ROI_DEVICE=0` keeps the torch chain; `det.roi_paths` counts the calls of each."""
+(`TwoStageDetector.device_path_reason`), `S2D_ROI_DEVICE=0` keeps the torch chain; `det.roi_paths` counts the calls of each.
+
+RoI MLP at inference (csrc/roi_mlp.hip; `roi_mlp_reference`, `roi_mlp_fused`, `RoIHead.mlp_reason`): on the device path the eval-mode MLP - shared_fc_layer,
+cls_layers, reg_layers - is ONE fused fp32 MFMA launch from a packed weight image and a scale / shift vector cached on the head.  Training mode, a required
+gradient, a head outside the kernel's shape family or `S2D_ROI_MLP=0` keep the three nn.Sequential's; `head.mlp_paths` counts the calls of each."""
 import ctypes
 import os
 
@@ -229,6 +233,70 @@ def refine_rois(rois, roi_scores, roi_labels, rcnn_cls, rcnn_reg):
     return boxes, scores, labels
 
 
+def _mlp_chain(seq):
+    """the (conv, batch norm | None) pairs of one of RoIHead's nn.Sequential's, or None when it holds anything but
+    Conv1d(kernel_size=1) [+ BatchNorm1d + ReLU] [+ Dropout] groups"""
+    out, mods, i = [], list(seq), 0
+    while i < len(mods):
+        conv = mods[i]
+        if not isinstance(conv, nn.Conv1d) or conv.kernel_size != (1,) or conv.stride != (1,) or conv.groups != 1 or conv.padding not in ((0,), "valid"):
+            return None
+        i += 1
+        bn = None
+        if i < len(mods) and isinstance(mods[i], nn.BatchNorm1d):
+            bn = mods[i]
+            if i + 1 >= len(mods) or not isinstance(mods[i + 1], nn.ReLU) or bn.running_mean is None or bn.weight is None:
+                return None
+            i += 2
+        if i < len(mods) and isinstance(mods[i], nn.Dropout):
+            i += 1
+        out.append((conv, bn))
+    return out
+
+
+def _mlp_affine(conv, bn):
+    """(scale, shift) of y = act(scale * (x . W^T) + shift): eval batch norm behind the convolution, or the convolution's own bias"""
+    if bn is None:
+        scale = torch.ones_like(conv.weight[:, 0, 0])
+        return scale, (conv.bias if conv.bias is not None else torch.zeros_like(scale))
+    scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+    mean = bn.running_mean if conv.bias is None else bn.running_mean - conv.bias
+    return scale, bn.bias - mean * scale
+
+
+def roi_mlp_reference(head, feats):
+    """The eval-mode MLP of `head` (a RoIHead) restated from its parameters: feats [..., cin] -> (rcnn_cls [R, num_class], rcnn_reg [R,
+    code_size]), R = the product of the leading dimensions.  Every layer is act(scale * F.linear(x, W) + shift) with scale = gamma /
+    sqrt(running_var + eps), shift = beta - running_mean * scale behind a batch norm and scale = 1, shift = bias on the two final
+    convolutions; dropout is the identity.  Any dtype (the parameters' and the features' must agree), any device: this is the definition
+    csrc/roi_mlp.hip implements, and in float64 the oracle it is tested against."""
+    def run(seq, x):
+        chain = _mlp_chain(seq)
+        if chain is None:
+            raise NotImplementedError("roi_mlp_reference: a chain of Conv1d(kernel_size=1) [+ BatchNorm1d + ReLU] groups expected")
+        for conv, bn in chain:
+            scale, shift = _mlp_affine(conv, bn)
+            x = F.linear(x, conv.weight.squeeze(-1)) * scale + shift
+            if bn is not None:
+                x = F.relu(x)
+        return x
+    with torch.no_grad():
+        shared = run(head.shared_fc_layer, feats.reshape(-1, feats.shape[-1]))
+        return run(head.cls_layers, shared), run(head.reg_layers, shared)
+
+
+ROI_MLP_MAX_CIN, ROI_MLP_MAX_WIDTH = 4096, 256   # s2d_roi_mlp_supported
+
+
+def roi_mlp_fused(head, feats):
+    """(rcnn_cls [R, 1], rcnn_reg [R, 7]) of feats [..., cin] through the fused kernel of csrc/roi_mlp.hip - what
+    RoIHead.forward(training=False, device=True) runs.  Raises with `head.mlp_reason(feats)` when the kernel does not apply: no fallback."""
+    reason, spec = head._mlp_check(feats)
+    if reason is not None:
+        raise _lib.S2DError(f"roi_mlp_fused: {reason}")
+    return head._mlp_fused(feats, spec)
+
+
 class ProposalTargetLayer(nn.Module):
     """IoU-based sampling of the first stage's RoIs and their classification / regression labels
     (proposal_target_layer.py).  The random draws are the reference's (np.random.permutation / np.random.rand on the host,
@@ -404,6 +472,8 @@ class RoIHead(nn.Module):
         target_cfg = _cfg_get(model_cfg, "TARGET_CONFIG", None)
         self.proposal_target_layer = ProposalTargetLayer(target_cfg) if target_cfg else None   # no parameters: state_dict unchanged
         self.forward_ret_dict = None
+        self.mlp_paths = {"fused": 0, "torch": 0}   # calls of forward() by the path their MLP took
+        self._mlp_cache = None                      # the fused kernel's layer table, packed weight image and scale / shift vector
 
     def assign_targets(self, batch_dict):
         """sampled RoIs + their ground-truth boxes encoded in the RoI's frame (roi_head_template.py:43-92)"""
@@ -527,6 +597,116 @@ class RoIHead(nn.Module):
                 t["roi_features"] = batch_dict["roi_features"][torch.arange(bs, device=rois.device)[:, None], table[0].long()]
         return t
 
+    def _mlp_spec(self):
+        """(cin, shared widths, cls hidden widths, reg hidden widths, chains) of the three nn.Sequential's, or the reason (str) why
+        they lie outside the shape family of csrc/roi_mlp.hip"""
+        chains = [_mlp_chain(m) for m in (self.shared_fc_layer, self.cls_layers, self.reg_layers)]
+        if any(c is None for c in chains):
+            return "layers other than Conv1d(kernel_size=1) [+ BatchNorm1d + ReLU] groups"
+        shared, cls, reg = chains
+        if any(bn is None for _, bn in shared) or any(bn is None for _, bn in cls[:-1] + reg[:-1]) or not cls or not reg \
+                or cls[-1][1] is not None or reg[-1][1] is not None:
+            return "hidden layers without a batch norm, or a final layer with one"
+        if self.code_size != 7 or self.num_class != 1:
+            return f"code_size {self.code_size}, num_class {self.num_class} (code size 7 and one RoI class only)"
+        if not 1 <= len(shared) <= 2:
+            return f"{len(shared)} shared layers (1 or 2)"
+        if len(cls) - 1 > 2 or len(reg) - 1 > 2:
+            return f"{len(cls) - 1} cls / {len(reg) - 1} reg hidden layers (at most 2 each)"
+        cin = shared[0][0].in_channels
+        if cin % 4 != 0 or not 4 <= cin <= ROI_MLP_MAX_CIN:
+            return f"{cin} input channels (a multiple of 4, at most {ROI_MLP_MAX_CIN})"
+        widths = [[c.out_channels for c, _ in shared], [c.out_channels for c, _ in cls[:-1]], [c.out_channels for c, _ in reg[:-1]]]
+        for w in sum(widths, []):
+            if w % 16 != 0 or not 16 <= w <= ROI_MLP_MAX_WIDTH:
+                return f"width {w} (multiples of 16, at most {ROI_MLP_MAX_WIDTH})"
+        if cls[-1][0].out_channels != 1 or reg[-1][0].out_channels != 7:
+            return f"final layers of {cls[-1][0].out_channels} and {reg[-1][0].out_channels} channels (1 and 7)"
+        return (cin, *widths, shared + cls + reg)
+
+    def _mlp_check(self, feats):
+        """(reason | None, spec)"""
+        if os.environ.get("S2D_ROI_MLP") == "0":
+            return "S2D_ROI_MLP=0", None
+        if self.training:
+            return "the head is in training mode (batch statistics, dropout)", None
+        spec = self._mlp_spec()
+        if isinstance(spec, str):
+            return spec, None
+        if not (torch.is_tensor(feats) and feats.is_cuda):
+            return "the features are not a CUDA tensor (CPU tensor)", None
+        if feats.dtype != torch.float32:
+            return f"feature dtype {feats.dtype}", None
+        if feats.shape[-1] != spec[0]:
+            return f"{feats.shape[-1]} feature channels for a head of {spec[0]}", None
+        tensors = []
+        for conv, bn in spec[4]:
+            tensors += [conv.weight, conv.bias] if bn is None else [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        tensors = [t for t in tensors if t is not None]
+        if any(t.device != feats.device or t.dtype != torch.float32 for t in tensors):
+            return "parameters on another device or not fp32", None
+        if torch.is_grad_enabled() and (feats.requires_grad or any(t.requires_grad for t in tensors)):
+            return "a gradient is required (no backward through the fused MLP)", None
+        return None, spec
+
+    def mlp_reason(self, feats):
+        """None when forward(training=False, device=True) can run the MLP as the one fused launch of csrc/roi_mlp.hip, else why it
+        runs the three nn.Sequential's through torch"""
+        return self._mlp_check(feats)[0]
+
+    def _mlp_images(self, spec, dev):
+        """(plan, packed weight image, scale / shift vector) of the fused MLP, cached on the head.  Keyed like dense2d.cached_pack on
+        (data_ptr, _version) of every tensor that enters each of the two: an optimizer step, load_state_dict or an in-place edit of a
+        running statistic rebuilds what it changed (and only that); dense2d.clear_pack_cache() - checkpoint.load - and
+        dense2d.refresh_pack_cache() - the fused Adam, which writes through raw pointers - drop both."""
+        from . import dense2d
+        cin, shared_w, cls_w, reg_w, chain = spec
+        lib = _lib.load()
+        cache = self._mlp_cache
+        shape = (cin, tuple(shared_w), tuple(cls_w), tuple(reg_w), str(dev), dense2d.pack_epoch())
+        if cache is None or cache["shape"] != shape:
+            pad = lambda w: (list(w) + [0, 0])[:2]
+            plan = _lib.RoiMlpPlan()
+            _lib.check(lib.s2d_roi_mlp_plan_make(cin, len(shared_w), *pad(shared_w), len(cls_w), *pad(cls_w), len(reg_w), *pad(reg_w), self.num_class,
+                                                 self.code_size, ctypes.byref(plan)), "s2d_roi_mlp_plan_make")
+            cache = self._mlp_cache = dict(shape=shape, plan=plan, w_key=None, packed=None, a_key=None, affine=None)
+        plan = cache["plan"]
+        key = lambda ts: tuple((t.data_ptr(), t._version) for t in ts if t is not None)
+        w_key = key([conv.weight for conv, _ in chain])
+        if cache["w_key"] != w_key:
+            weights = [conv.weight.detach() for conv, _ in chain]   # [cout, cin, 1] contiguous = [cout][cin] row-major
+            weights = [w if w.is_contiguous() else w.contiguous() for w in weights]
+            packed = torch.empty((plan.packed_elems,), dtype=torch.float32, device=dev)
+            ptrs = (ctypes.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
+            _lib.check(lib.s2d_roi_mlp_pack(ctypes.byref(plan), ptrs, packed.data_ptr(), torch._C._cuda_getCurrentRawStream(dev.index)), "s2d_roi_mlp_pack")
+            cache["w_key"], cache["packed"] = w_key, packed
+        # (a training-mode batch norm moves its running statistics WITHOUT moving their version counters - torch.batch_norm does not declare
+        # them as written - but it counts the call in num_batches_tracked with an ordinary in-place add: that counter is part of the key)
+        a_key = key([t for conv, bn in chain for t in ((conv.bias,) if bn is None else
+                                                       (conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked))])
+        if cache["a_key"] != a_key:
+            parts = []
+            with torch.no_grad():
+                for l, (conv, bn) in enumerate(chain):
+                    fill = plan.layer[l].cout_pad - conv.out_channels
+                    parts += [F.pad(v.float(), (0, fill)) for v in _mlp_affine(conv, bn)]
+                affine = torch.cat(parts).contiguous()
+            assert affine.numel() == plan.affine_elems
+            cache["a_key"], cache["affine"] = a_key, affine
+        return plan, cache["packed"], cache["affine"]
+
+    def _mlp_fused(self, feats, spec):
+        """rcnn_cls [R, 1], rcnn_reg [R, 7] of feats [..., cin] in one launch"""
+        lib, dev, st = _device_args("roi_mlp", feats)
+        x = feats.detach().reshape(-1, feats.shape[-1])
+        x = x if x.is_contiguous() and x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
+        plan, packed, affine = self._mlp_images(spec, dev)
+        rcnn_cls = torch.empty((x.shape[0], 1), dtype=torch.float32, device=dev)
+        rcnn_reg = torch.empty((x.shape[0], 7), dtype=torch.float32, device=dev)
+        _lib.check(lib.s2d_roi_mlp_run(ctypes.byref(plan), x.data_ptr(), x.shape[0], packed.data_ptr(), affine.data_ptr(), rcnn_cls.data_ptr(),
+                                       rcnn_reg.data_ptr(), st), "s2d_roi_mlp_run")
+        return rcnn_cls, rcnn_reg
+
     def forward(self, batch_dict, training=True, device=False):
         """device=True: targets (training) and refinement (inference) on the kernels of csrc/roi_head.hip - CUDA tensors, code size 7"""
         batch_dict["batch_size"] = len(batch_dict["rois"])
@@ -534,10 +714,16 @@ class RoIHead(nn.Module):
         if training:   # roi_head.py:76-80
             targets = self.assign_targets_device(batch_dict) if device else self.assign_targets(batch_dict)
             batch_dict["rois"], batch_dict["roi_labels"], batch_dict["roi_features"] = targets["rois"], targets["roi_labels"], targets["roi_features"]
-        pooled = batch_dict["roi_features"].reshape(-1, 1, batch_dict["roi_features"].shape[-1]).permute(0, 2, 1).contiguous()
-        shared = self.shared_fc_layer(pooled)
-        rcnn_cls = self.cls_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
-        rcnn_reg = self.reg_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
+        reason, spec = self._mlp_check(batch_dict["roi_features"]) if device and not training else ("training or the torch chain", None)
+        if reason is None:   # the whole eval MLP in one launch (csrc/roi_mlp.hip)
+            self.mlp_paths["fused"] += 1
+            rcnn_cls, rcnn_reg = self._mlp_fused(batch_dict["roi_features"], spec)
+        else:
+            self.mlp_paths["torch"] += 1
+            pooled = batch_dict["roi_features"].reshape(-1, 1, batch_dict["roi_features"].shape[-1]).permute(0, 2, 1).contiguous()
+            shared = self.shared_fc_layer(pooled)
+            rcnn_cls = self.cls_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
+            rcnn_reg = self.reg_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
         if training:
             targets["rcnn_cls"], targets["rcnn_reg"] = rcnn_cls, rcnn_reg
             self.forward_ret_dict = targets

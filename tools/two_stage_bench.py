@@ -10,9 +10,14 @@ proposals, map and loss dictionary to every call and launches nothing, so the HI
 stage only: pack / BEV features / (match, sampling, targets) / RoI MLP / (refine or the two RoI losses).  Per row: median (min) of
 `runs` calls after `warmup`, the two paths alternating; the host wall clock of the same calls; kernel launches, device-to-host copy
 records and blocking runtime calls per call from a torch.profiler trace of one extra call; whether both paths return the same numbers.
-Training runs under a fixed seed (numpy, torch), set before every call, so both paths sample the same RoIs.  Last: the feature kernel
-alone against the bytes it has to move (four 1 KiB taps per sample point in, one fp32 row out)."""
+Training runs under a fixed seed (numpy, torch), set before every call, so both paths sample the same RoIs.  The inference row has
+three columns: the device path with the fused RoI MLP (csrc/roi_mlp.hip), the device path with the torch MLP (S2D_ROI_MLP=0: the row
+of the commit before the fused kernel) and the torch chain.  Then the feature kernel alone against the bytes it has to move (four 1 KiB
+taps per sample point in, one fp32 row out), and the RoI MLP alone on the inference row's [B * 500, 2560] features: the fused launch
+against the head's three nn.Sequential's, with their launch counts and their largest absolute errors against the float64 definition
+(second_stage.roi_mlp_reference) - e_chain and e_fused of tests/test_roi_mlp_gpu.py - and the fused launch at other row counts."""
 import argparse
+import copy
 import os
 import statistics
 import sys
@@ -87,7 +92,8 @@ def main():
              f"({', '.join(str(len(p['scores'])) for p in preds)}), {GT} ground-truth boxes per sample"]
 
     def call(path, training):
-        os.environ["S2D_ROI_DEVICE"] = "1" if path == "device" else "0"
+        os.environ["S2D_ROI_DEVICE"] = "0" if path == "torch" else "1"
+        os.environ["S2D_ROI_MLP"] = "1" if path == "fused" else "0"
         if training:
             np.random.seed(7); torch.manual_seed(7)
             out = det({"gt_boxes_and_cls": gt}, return_loss=True)
@@ -100,8 +106,9 @@ def main():
     for title, training in (("inference (eval, no_grad): features of all proposals, RoI MLP, refine", False),
                             ("training forward + RoI losses (fixed seed): match, sampling, targets, features of the 128 sampled RoIs per sample, RoI MLP", True)):
         det.train(training)
-        paths = {k: (lambda k=k: call(k, training)) for k in ("device", "torch")}
-        before = dict(det.roi_paths)
+        names = ("device", "torch") if training else ("fused", "device", "torch")   # (the training branch keeps the torch MLP)
+        paths = {k: (lambda k=k: call(k, training)) for k in names}
+        before, mlp_before = dict(det.roi_paths), dict(det.roi_head.mlp_paths)
         for fn in paths.values():
             for _ in range(args.warmup):
                 fn()
@@ -113,18 +120,23 @@ def main():
                 ev[k].append(e)
                 wall[k].append(w)
         n = args.warmup + args.runs
-        assert det.roi_paths["device"] - before["device"] == n and det.roi_paths["torch"] - before["torch"] == n, det.roi_paths
+        assert det.roi_paths["device"] - before["device"] == n * (len(names) - 1) and det.roi_paths["torch"] - before["torch"] == n, det.roi_paths
+        assert det.roi_head.mlp_paths["fused"] - mlp_before["fused"] == (0 if training else n), det.roi_head.mlp_paths
         try:
             cnt = {k: counts_of(fn) for k, fn in paths.items()}
             cnt_text = {k: f"{v[0]} launches, {v[1]} device-to-host copy records, {sum(v[2].values())} blocking runtime calls "
                            f"({', '.join(f'{n} x {c}' for n, c in sorted(v[2].items())) or 'none'})" for k, v in cnt.items()}
         except Exception as exc:   # the counts are a side figure: the timing above stands without them
             cnt_text = {k: f"launch count not taken ({type(exc).__name__})" for k in paths}
-        lines.append(f"{title}: outputs agree: {agree(out['device'], out['torch'], training)}")
+        lines.append(f"{title}: outputs agree: {all(agree(out[k], out['torch'], training) for k in names[:-1])}")
         for k in paths:
             lines.append(f"    {k:6s} {statistics.median(ev[k]):8.3f} ms ({min(ev[k]):.3f})   host wall {statistics.median(wall[k]):8.3f} ms   {cnt_text[k]}")
         ratio = statistics.median(ev["torch"]) / statistics.median(ev["device"])
         lines.append(f"    torch / device = x{ratio:.2f}" + ("" if ratio >= 1 else "   (device path SLOWER on this run)"))
+        if not training:
+            ratio = statistics.median(ev["device"]) / statistics.median(ev["fused"])
+            lines.append(f"    device / fused = x{ratio:.2f}, torch / fused = x{statistics.median(ev['torch']) / statistics.median(ev['fused']):.2f}"
+                         + ("" if ratio >= 1 else "   (fused MLP SLOWER on this run)"))
 
     # the feature kernel alone: 4 taps of C bf16 per sample point in, C fp32 per sample point out
     boxes = torch.cat([p["box3d_lidar"] for p in preds])
@@ -146,6 +158,57 @@ def main():
         lines.append(f"roi_bev_features alone, {what}: {pts} sample points, {moved / 1e6:.2f} MB to move (taps in, fp32 rows out; the chain's fp32 NHWC "
                      f"copy alone writes {B * HW * HW * C * 4 / 1e6:.0f} MB), median {statistics.median(t) * 1e3:.1f} us (min {min(t) * 1e3:.1f}) "
                      f"= {moved / statistics.median(t) / 1e6:.1f} GB/s including the launch")
+    # the RoI MLP alone on the inference row's features: one fused launch against the three nn.Sequential's
+    det.eval()
+    os.environ["S2D_ROI_MLP"] = "1"
+    head = det.roi_head
+    row = np.full((B, 500), -1, np.int32)
+    off = 0
+    for b, p in enumerate(preds):
+        row[b, :len(p["scores"])] = off + np.arange(len(p["scores"]))
+        off += len(p["scores"])
+    feats = S.roi_bev_features(bev, boxes, torch.from_numpy(row).cuda(), ext.pc_start, ext.voxel_size, ext.out_stride, 5).view(B * 500, 5 * C)
+
+    def torch_mlp():
+        shared = head.shared_fc_layer(feats.reshape(-1, 1, feats.shape[-1]).permute(0, 2, 1).contiguous())
+        return (head.cls_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1), head.reg_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1))
+    with torch.no_grad():
+        mlp = {"fused": lambda: S.roi_mlp_fused(head, feats), "torch": torch_mlp}
+        for fn in mlp.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        t, res = {k: [] for k in mlp}, {}
+        for _ in range(args.runs):
+            for k, fn in mlp.items():
+                e, _, res[k] = one_call(fn)
+                t[k].append(e)
+        try:
+            launches = {k: str(counts_of(fn)[0]) for k, fn in mlp.items()}
+        except Exception as exc:
+            launches = {k: f"not counted ({type(exc).__name__})" for k in mlp}
+        head.forward_ret_dict = None   # (the training row's graph tensors do not copy)
+        ref = torch.cat(S.roi_mlp_reference(copy.deepcopy(head).double(), feats.double()), dim=1)
+    err = {k: float((torch.cat(res[k], dim=1).double() - ref).abs().max()) for k in mlp}
+    flop = 2 * feats.shape[0] * sum(l.cin * l.cout for l in head._mlp_cache["plan"].layer[:head._mlp_cache["plan"].num_layers])
+    ratio = statistics.median(t["torch"]) / statistics.median(t["fused"])
+    lines.append(f"RoI MLP alone, eval, {feats.shape[0]} x {feats.shape[1]} fp32 features -> 256 -> 256 -> 2 x (256 -> 256 -> 1 | 7), {flop / 1e9:.2f} GFLOP: "
+                 f"fused {statistics.median(t['fused']) * 1e3:.1f} us (min {min(t['fused']) * 1e3:.1f}), {launches['fused']} launches, "
+                 f"{flop / statistics.median(t['fused']) / 1e9:.1f} TFLOP/s including the launch; torch {statistics.median(t['torch']) * 1e3:.1f} us "
+                 f"(min {min(t['torch']) * 1e3:.1f}), {launches['torch']} launches; torch / fused = x{ratio:.2f}"
+                 + ("" if ratio >= 1 else "   (fused MLP SLOWER on this run)"))
+    lines.append(f"    largest absolute error against the float64 definition (max|out| {float(ref.abs().max()):.3f}): e_chain (torch fp32 MLP) {err['torch']:.3e}, "
+                 f"e_fused {err['fused']:.3e}; bound of the tests 4 * e_chain + 1e-7 * max|out| = {4 * err['torch'] + 1e-7 * float(ref.abs().max()):.3e}")
+    # the fused launch at other row counts (16 rows = one workgroup; 4 096 = one per CU): where it stops being latency-bound
+    scale = []
+    with torch.no_grad():
+        for rows in (16, 4096, 8000, 32000):
+            x = torch.randn(rows, 5 * C, device="cuda")
+            fn = lambda: S.roi_mlp_fused(head, x)
+            for _ in range(args.warmup):
+                fn()
+            scale.append(f"{rows} rows {statistics.median([one_call(fn)[0] for _ in range(args.runs)]) * 1e3:.1f} us")
+    lines.append(f"    fused launch alone by row count (random features, median of {args.runs}): {', '.join(scale)}")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
