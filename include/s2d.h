@@ -752,6 +752,24 @@ int s2d_masked_mse_bwd(const void *student, int student_bf16, const void *teache
                        const float *fwd_out4, const float *go, void *dstudent, s2d_stream_t stream);
 
 /*
+ * Feature loss of the PointPillars distillation branch (det3d/torchie/trainer/trainer.py:749-762): the four maps [n, c, h, w] are
+ * max-pooled 2x2 (floor mode) on the fly and five masked MSE terms of weight 10 are taken over the pooled values, the masks being
+ * pooled teacher > 0; the third term puts the `a` maps under the `b` mask.  sa, sb: the student's maps, one element type
+ * (student_bf16: 1 bf16, 0 fp32) and one memory order (student_nhwc: 1 channels_last, 0 planar); da, db: the teacher's, likewise.
+ * c % 8 == 0, h >= 2, w >= 2, 16-byte aligned maps; anything else is S2D_ERR_UNSUPPORTED.
+ * out8 (device) = loss, 20/nA, 20/(N-nA), 20/nB, 20/nB, 20/(N-nB), nA, nB.  Deterministic (no atomics), no host read, no memset.
+ * bwd: dsa, dsb (the student's element type and order) = go * dloss/dstudent, routed to each window's selected element by torch's
+ * max_pool2d rule (first of tied elements); every element is written once, zeros included.
+ */
+size_t s2d_pooled_distill_workspace_bytes(void);
+int s2d_pooled_distill_fwd(const void *sa, const void *sb, int student_bf16, int student_nhwc, const void *da, const void *db,
+                           int teacher_bf16, int teacher_nhwc, int n, int c, int h, int w, float *out8, void *ws, size_t ws_bytes,
+                           s2d_stream_t stream);
+int s2d_pooled_distill_bwd(const void *sa, const void *sb, int student_bf16, int student_nhwc, const void *da, const void *db,
+                           int teacher_bf16, int teacher_nhwc, int n, int c, int h, int w, const float *out8, const float *go,
+                           void *dsa, void *dsb, s2d_stream_t stream);
+
+/*
  * Fused PCR level heads + losses: gen_mask_k / gen_out_k (1x1x1 Conv3d C->1 / C->3, det3d/models/necks/rpn.py:273-275,292-294)
  * and mask_offset_loss (voxelnet.py:171-185) evaluated straight from the level's feature volume g[B][C][D*H*W] - the occupancy
  * logits, the offset volume and its zero-filled gradient are never written; the offset conv runs at the m recon voxels only.

@@ -234,6 +234,13 @@ SIGNATURES = {
                                           c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "s2d_masked_mse_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_f32p, c_f32p,
                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_pooled_distill_workspace_bytes": (ctypes.c_size_t, []),
+    "s2d_pooled_distill_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_int] + [ctypes.c_int] * 4 +
+                               [c_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_pooled_distill_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_int] + [ctypes.c_int] * 4 +
+                               [c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "s2d_pcr_heads_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "s2d_pcr_heads_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "s2d_pcr_heads_fwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32p, c_f32p, ctypes.c_int64] + [ctypes.c_int] * 5 +

@@ -29,8 +29,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # roi_head.hip likewise: its fp32 bilinear blends run in the same step, right behind predict (rule 36).
 # anchor_predict.hip is MultiGroupHead.predict's counterpart of center_predict.hip and is built like it (rule 36).
 # roi_mlp.hip: its scale / shift epilogue is a packed-FP32 candidate and it runs between roi_head.hip's launches (rule 36).
+# pillar_distill.hip: eight channels of fp32 differences, squares and sums per thread are packed-FP32 candidates, and the pillar student's
+# backward reaches its gradient kernel while weight gradients of the PCR head can still run on the side stream (rule 36).
 EXTRA = {"deform_conv.hip": ["-fno-slp-vectorize"], "center_predict.hip": ["-fno-slp-vectorize"], "roi_head.hip": ["-fno-slp-vectorize"],
-         "anchor_predict.hip": ["-fno-slp-vectorize"], "roi_mlp.hip": ["-fno-slp-vectorize"]}
+         "anchor_predict.hip": ["-fno-slp-vectorize"], "roi_mlp.hip": ["-fno-slp-vectorize"], "pillar_distill.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("S2D_BUILD_LOSSES_SLP") != "1":
     EXTRA["losses.hip"] = ["-fno-slp-vectorize"]
 

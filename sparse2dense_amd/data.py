@@ -152,17 +152,24 @@ class SyntheticNuscFrames(SyntheticFrames):
 class SyntheticPillarFrames:
     """Scene C: the same sweeps voxelized as pillars (0.32 m, 20 points, 32 000 pillars,
     configs/waymo/pp/...:156-162) plus the object-only cloud for the PCR target; targets on the
-    468 x 468 map (out_size_factor 1)."""
+    468 x 468 map (out_size_factor 1).  distill=True: the teacher's side of the pillar distillation step as well - the densified
+    cloud as `dense_*` pillars and the object-only cloud of the same `scene.make_distill_points` call as the `reconstruction_*` pillars."""
 
-    def __init__(self, batch_size, n_points=150000, seed=20240928, device="cuda"):
+    def __init__(self, batch_size, n_points=150000, seed=20240928, device="cuda", distill=False):
         self.device = torch.device(device)
+        self.distill = distill
         self.gen = VoxelGenerator(scene.PILLAR_VOXEL, scene.PILLAR_RANGE, 20, 32000)
-        self.points, self.recon_points = [], []
+        self.points, self.dense_points, self.recon_points = [], [], []
         tg = {k: [] for k in ["hm", "anno_box", "ind", "mask", "cat"]}
         for b in range(batch_size):
             s = scene.make_scene(n_points, seed=seed + b, pc_range=scene.PILLAR_RANGE)
             self.points.append(torch.from_numpy(s["points"]).to(self.device))
-            self.recon_points.append(torch.from_numpy(s["object_points"]).to(self.device))
+            if distill:
+                d, r = scene.make_distill_points(s, seed=seed + 100 + b)
+                self.dense_points.append(torch.from_numpy(d).to(self.device))
+                self.recon_points.append(torch.from_numpy(r).to(self.device))
+            else:
+                self.recon_points.append(torch.from_numpy(s["object_points"]).to(self.device))
             t = scene.assign_targets(s["gt_boxes"], s["gt_classes"], pc_range=scene.PILLAR_RANGE,
                                      voxel_size=scene.PILLAR_VOXEL, out_size_factor=1, grid_xy=(468, 468))
             for k in tg:
@@ -172,6 +179,8 @@ class SyntheticPillarFrames:
 
     def example(self):
         ex = voxelize_batch(self.gen, self.points)
+        if self.distill:
+            ex.update(voxelize_batch(self.gen, self.dense_points, prefix="dense_"))
         ex.update(voxelize_batch(self.gen, self.recon_points, prefix="reconstruction_"))
         ex["shape"] = np.stack([self.grid_size] * len(self.points))
         ex.update(self.targets)

@@ -304,6 +304,78 @@ def sparse2dense_loss(F_S_a, F_D_a, F_S_b, F_D_b):
     return masked_mse_pair(F_S_a, F_D_a, 10.0, 20.0) + masked_mse_pair(F_S_b, F_D_b, 5.0, 20.0)
 
 
+class _PooledDistillFn(torch.autograd.Function):
+    """the PointPillars feature loss over 2x2 max-pooled maps, pooling included: 2 launches forward, 1 backward (csrc/pillar_distill.hip)"""
+
+    @staticmethod
+    def _args(sa, sb, da, db):
+        n, c, h, w = sa.shape
+        return (sa.data_ptr(), sb.data_ptr(), int(sa.dtype == torch.bfloat16), _pooled_pair_order(sa, sb), da.data_ptr(), db.data_ptr(),
+                int(da.dtype == torch.bfloat16), _pooled_pair_order(da, db), n, c, h, w)
+
+    @staticmethod
+    def forward(ctx, sa, sb, da, db):
+        from . import _lib
+        from .dense2d import _ptr, _stream, _ws
+        lib = _lib.load()
+        out = torch.empty(8, dtype=torch.float32, device=sa.device)
+        ws = _ws(lib.s2d_pooled_distill_workspace_bytes(), sa.device)
+        _lib.check(lib.s2d_pooled_distill_fwd(*_PooledDistillFn._args(sa, sb, da, db), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+                   "s2d_pooled_distill_fwd")
+        ctx.save_for_backward(sa, sb, da, db, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, go):
+        from . import _lib
+        from .dense2d import _ptr, _stream
+        sa, sb, da, db, out = ctx.saved_tensors
+        dsa, dsb = torch.empty_like(sa), torch.empty_like(sb)   # same strides; the kernel writes every element
+        _lib.check(_lib.load().s2d_pooled_distill_bwd(*_PooledDistillFn._args(sa, sb, da, db), _ptr(out), _ptr(go.float().reshape(1).contiguous()),
+                                                      dsa.data_ptr(), dsb.data_ptr(), _stream()), "s2d_pooled_distill_bwd")
+        return dsa, dsb, None, None
+
+
+def _pooled_pair_order(a, b):
+    """the dense memory order two maps share: 0 planar, 1 channels_last, None neither"""
+    if a.is_contiguous() and b.is_contiguous():
+        return 0
+    if a.is_contiguous(memory_format=torch.channels_last) and b.is_contiguous(memory_format=torch.channels_last):
+        return 1
+    return None
+
+
+def _pooled_pair_ok(a, b):
+    """two maps of one covered dtype and one dense memory order"""
+    return (a.is_cuda and b.is_cuda and a.dtype == b.dtype and a.dtype in (torch.bfloat16, torch.float32)
+            and _pooled_pair_order(a, b) is not None and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
+
+
+def pooled_distill_loss(F_S_a, F_D_a, F_S_b, F_D_b):
+    """Feature loss of the PointPillars distillation branch (trainer.py:749-762): all four maps max-pooled 2x2, then
+    10 * [MSE_{~A} + MSE_A + MSE_Bm of (sa, da) + MSE_Bm + MSE_{~Bm} of (sb, db)] with A = da > 0, Bm = db > 0 - the third term puts the
+    `a` maps under the `b` mask, as the reference does.  The teacher carries no gradient.
+
+    CUDA maps [n, c, h, w] with c % 8 == 0, h, w >= 2, each pair (student, teacher) of one dtype (bf16 / fp32) and one memory order
+    (planar / channels_last) take the fused kernels; S2D_PILLAR_DISTILL_FUSED=0 switches them off.  Everything else takes the torch
+    restatement below: masked sums and counts, no boolean-indexed copies, in the maps' precision (bf16 maps in fp32)."""
+    F_D_a, F_D_b = F_D_a.detach(), F_D_b.detach()
+    if (os.environ.get("S2D_PILLAR_DISTILL_FUSED", "1") != "0" and F_S_a.dim() == 4 and F_S_a.shape[1] % 8 == 0 and min(F_S_a.shape[2:]) >= 2
+            and F_S_a.shape == F_D_a.shape == F_S_b.shape == F_D_b.shape and _pooled_pair_ok(F_S_a, F_S_b) and _pooled_pair_ok(F_D_a, F_D_b)):
+        return _PooledDistillFn.apply(F_S_a, F_S_b, F_D_a, F_D_b)
+    if F_S_a.dtype != torch.float64:
+        F_S_a, F_D_a, F_S_b, F_D_b = F_S_a.float(), F_D_a.float(), F_S_b.float(), F_D_b.float()
+    sa, da, sb, db = (F.max_pool2d(t, 2, 2) for t in (F_S_a, F_D_a, F_S_b, F_D_b))
+    A, Bm = da > 0, db > 0
+    n = A.numel()
+    nA, nB = A.sum(), Bm.sum()
+    d2, e2 = (sa - da) ** 2, (sb - db) ** 2
+    zero = d2.new_zeros(())
+    sum_A, sum_aB, sum_bB = torch.where(A, d2, zero).sum(), torch.where(Bm, d2, zero).sum(), torch.where(Bm, e2, zero).sum()
+    # an empty class gives nan, as torch's mean of nothing does
+    return 10.0 * ((d2.sum() - sum_A) / (n - nA) + sum_A / nA + sum_aB / nB + sum_bB / nB + (e2.sum() - sum_bB) / (n - nB))
+
+
 DEBUG_SUMS = []
 
 

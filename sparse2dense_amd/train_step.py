@@ -1,5 +1,5 @@
 """One training iteration of the hot path: what `Trainer.batch_processor_inline` and
-`TS_Trainer.batch_processor_inline` (CenterPoint branch) compute
+`TS_Trainer.batch_processor_inline` (PointPillars and CenterPoint branches) compute
 (/root/reference/det3d/torchie/trainer/trainer.py:432-459,726-811) followed by
 `OptimizerHook.after_train_iter` (hooks/optimizer.py:15-21: zero_grad, backward, clip 35).
 
@@ -9,7 +9,7 @@ The teacher/student branch in the reference is chosen by `T_model.backbone._get_
 import torch
 import torch.nn.functional as F
 
-from .heads import distill_reg_loss, fast_focal_loss, sparse2dense_loss
+from .heads import distill_reg_loss, fast_focal_loss, pooled_distill_loss, sparse2dense_loss
 
 
 def _unwrap(m):
@@ -29,8 +29,31 @@ def single_stage_loss(model, example):
     return parse_losses(losses), losses
 
 
+def distill_loss_pillar(T_model, S_model, example):
+    """PointPillars branch (trainer.py:741-773): the teacher's dense and object-only canvases against the student's S2D maps, all four
+    max-pooled 2x2, five MSE terms of weight 10 (heads.pooled_distill_loss), the heat-map focal term, PCR losses at 0.5, no kd_reg term."""
+    T_model.eval()
+    with torch.no_grad():
+        T_preds, F_D_a, F_D_b = T_model(example, return_loss=False)
+    losses, F_S_a, F_S_b, S_preds, mask_loss, offset_loss = S_model(example, return_loss=True)
+    s2d = pooled_distill_loss(F_S_a, F_D_a, F_S_b, F_D_b)
+    ind, mask, cat = example["ind"][0], example["mask"][0], example["cat"][0]
+    t_hm = torch.sigmoid(T_preds[0]["hm"]).detach()
+    kd_hm = fast_focal_loss(S_preds[0]["hm"], t_hm, ind, mask, cat)
+    losses["loss"][0] = losses["loss"][0] + (s2d + kd_hm) + (mask_loss + offset_loss) * 0.5
+    losses["sparse2dense_loss"] = [s2d.detach()]
+    losses["mask_loss"] = [mask_loss.detach()]
+    losses["reconstruction_loss"] = [offset_loss.detach()]
+    losses["T_hm_loss"] = [fast_focal_loss(t_hm, example["hm"][0], ind, mask, cat).detach()]
+    losses["kd_hm_loss"] = [kd_hm.detach()]
+    return parse_losses(losses), losses
+
+
 def distill_loss(T_model, S_model, example):
-    """Teacher (eval, no grad) + student forward and every S2D loss term (trainer.py:775-811)."""
+    """Teacher (eval, no grad) + student forward and every S2D loss term (trainer.py:775-811).  A teacher whose backbone is a
+    PointPillarsScatter takes the PointPillars branch (trainer.py:741: `distill_loss_pillar`)."""
+    if type(getattr(_unwrap(T_model), "backbone", None)).__name__ == "PointPillarsScatter":
+        return distill_loss_pillar(T_model, S_model, example)
     T_model.eval()
     with torch.no_grad():
         T_preds, F_D_a, F_D_b = T_model(example, return_loss=False, return_feature=True, return_recon_feature=True)
