@@ -1270,6 +1270,51 @@ int s2d_roi_mlp_pack(const s2d_roi_mlp_plan *plan, const float *const *weights, 
 int s2d_roi_mlp_run(const s2d_roi_mlp_plan *plan, const float *feats, int64_t rows, const float *packed, const float *affine, float *rcnn_cls,
                     float *rcnn_reg, s2d_stream_t stream);
 
+/*
+ * Frame preparation of the S2D data step (csrc/prep.hip; det3d/datasets/pipelines/preprocess.py:81-117,178-201,257-260).  points
+ * [n_points][ncols] and obj_points [obj_rows][ncols] fp32 with x, y, z first; boxes [num_boxes][box_dim] fp32 with the centre in
+ * columns 0-2, the size in 3-5 and the yaw in the LAST column; num_boxes <= S2D_PREP_MAX_BOXES, row counts <= S2D_PREP_MAX_POINTS.
+ *
+ * Inside test (box_np_ops.py:641-647, geometry.py:215-276; strict on all six faces), fp32: with d = p - centre,
+ *   |d.x cos r - d.y sin r| < dim0 / 2,  |d.x sin r + d.y cos r| < dim1 / 2,  |d.z| < dim2 / 2,
+ * cos r and sin r evaluated in double from the fp32 yaw and rounded to fp32.
+ *
+ * s2d_prep_points_in_rbbox: mask [n_points][num_boxes] bytes (0 / 1) and / or counts [num_boxes] int32, either may be NULL (not both).
+ *
+ * s2d_prep_compose_count + s2d_prep_compose_fill (training mode, distillation): kinds [num_boxes] int8 (0 other, 1 VEHICLE, 2 SIGN);
+ * obj_offsets [num_boxes + 1] int32 DEVICE array, the stored cloud of box j = rows obj_offsets[j] .. obj_offsets[j + 1] of obj_points
+ * in the object's own frame (entries are clamped to 0 .. obj_rows on the device).  A box with an empty range, and every SIGN, takes the
+ * frame's own points inside it.  A stored VEHICLE keeps the side y > 0 or y < 0 with strictly more points (a tie takes y < 0; y == 0
+ * is dropped) and appends that side's mirror image; stored rows are rotated by pi / 2 + yaw about z (x' = x c + y s, y' = -x s + y c)
+ * and moved to the box centre.  dense = the points outside every box in input order, then each box's block in box order (a point in
+ * two boxes appears in both blocks); reconstruction = the blocks of the boxes that are no SIGN, in order, without the rows that lie
+ * in no box of the frame.  _count runs four launches and leaves totals[0] = dense rows, totals[1] = reconstruction rows, totals[2] = the
+ * number of boxes that are no SIGN (device int32[3], the one read the host needs); _fill, one launch, writes both clouds from the SAME workspace, untouched in between, and
+ * never writes past dense_rows / recon_rows.
+ *
+ * s2d_prep_global_noise (core/sampler/preprocess.py:859-908,790-813,902-908,1032-1056): one launch over up to three clouds, columns
+ * 0-2 in place: y = -y (flip_x), x = -x (flip_y), x' = x c + y s, y' = -x s + y c, all three times scale, then (translate != 0) plus
+ * tx, ty, tz added in double.  The draws are the caller's.
+ *
+ * s2d_prep_gather_rows: dst[i] = src[perm[i]], perm [rows] int64 (the host's shuffle); dst must not alias src; a perm entry outside
+ * 0 .. rows - 1 leaves its row unwritten.
+ */
+#define S2D_PREP_MAX_BOXES 512
+#define S2D_PREP_MAX_POINTS (1 << 28)
+size_t s2d_prep_workspace_bytes(int64_t n_points, int num_boxes, int64_t obj_rows);
+int s2d_prep_points_in_rbbox(const float *points, int64_t n_points, int ncols, const float *boxes, int num_boxes, int box_dim, uint8_t *mask,
+                             int32_t *counts, void *ws, size_t ws_bytes, s2d_stream_t stream);
+int s2d_prep_compose_count(const float *points, int64_t n_points, int ncols, const float *boxes, int num_boxes, int box_dim,
+                           const int8_t *kinds, const float *obj_points, int64_t obj_rows, const int32_t *obj_offsets, void *ws,
+                           size_t ws_bytes, int32_t *totals, s2d_stream_t stream);
+int s2d_prep_compose_fill(const float *points, int64_t n_points, int ncols, int num_boxes, const float *obj_points, int64_t obj_rows,
+                          const void *ws, size_t ws_bytes, float *dense, int64_t dense_rows, float *recon, int64_t recon_rows,
+                          s2d_stream_t stream);
+int s2d_prep_global_noise(float *cloud0, int64_t rows0, float *cloud1, int64_t rows1, float *cloud2, int64_t rows2, int ncols, int flip_x,
+                          int flip_y, float rot_cos, float rot_sin, float scale, int translate, double tx, double ty, double tz,
+                          s2d_stream_t stream);
+int s2d_prep_gather_rows(const float *src, int64_t rows, int ncols, const int64_t *perm, float *dst, s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -468,6 +468,19 @@ SIGNATURES = {
     "s2d_roi_mlp_plan_make": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.POINTER(RoiMlpPlan)]),
     "s2d_roi_mlp_pack": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]),
     "s2d_roi_mlp_run": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    # frame preparation: inside test, dense / reconstruction clouds, global noise, shuffle gather (csrc/prep.hip)
+    "s2d_prep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
+    "s2d_prep_points_in_rbbox": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_prep_compose_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_prep_compose_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p]),
+    "s2d_prep_global_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [ctypes.c_int] +
+                              [ctypes.c_double] * 3 + [ctypes.c_void_p]),
+    "s2d_prep_gather_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -102,6 +102,67 @@ class SyntheticFrames:
         return ex
 
 
+class PreparedFrames(SyntheticFrames):
+    """Raw frames through the S2D data step on the device: every `example()` runs `prep.S2DPreprocess` (cloud composition, global noise,
+    shuffle; the draws come from `np.random`) on each frame, then the voxelizer and the target assignment `SyntheticFrames` uses, and
+    yields the keys `SyntheticFrames(distill=True)` yields.
+
+    frames: a list of dictionaries with `points` [N, 5], `gt_boxes` [M, 9] (velocity columns, yaw last: what the target assignment takes), `gt_names` [M] (the kinds follow from them:
+    VEHICLE, SIGN, other) and `objects`, one [P_j, 5] completed cloud in the object's own frame or None per box.  cfg: the `Preprocess`
+    keys of the reference's training config (mode "train", distillation True, db_sampler None); the default is the Waymo distillation
+    config's noise with three classes."""
+
+    DEFAULT_CFG = dict(mode="train", shuffle_points=True, distillation=True, global_rot_noise=[-0.78539816, 0.78539816],
+                       global_scale_noise=[0.95, 1.05], global_translate_std=0.5, db_sampler=None, class_names=list(scene.WAYMO_CLASS_NAMES),
+                       no_augmentation=False)
+
+    def __init__(self, frames, cfg=None, device="cuda", anchor_targets=None):
+        from . import prep
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise prep._lib.S2DError("PreparedFrames needs a CUDA device (no CPU fallback)")
+        self.distill = True
+        self.anchor_targets = anchor_targets
+        self.gens = waymo_generators(True)
+        self.grid_size = self.gens[""].grid_size
+        self.targets = None
+        self.cfg = dict(self.DEFAULT_CFG if cfg is None else cfg)
+        if self.cfg.get("mode") != "train" or not self.cfg.get("distillation"):
+            raise prep._lib.S2DError("PreparedFrames: a training config with distillation=True expected")
+        self.frames = []
+        for f in frames:
+            names = [str(n) for n in f["gt_names"]]
+            signs = [f"object_{j}" for j in range(len(names))]
+            objects = {s: torch.from_numpy(np.ascontiguousarray(g, dtype=np.float32)).to(self.device)
+                       for s, g in zip(signs, f["objects"]) if g is not None and len(g)}
+            self.frames.append(dict(points=torch.from_numpy(np.ascontiguousarray(f["points"], dtype=np.float32)).to(self.device),
+                                    boxes=np.ascontiguousarray(f["gt_boxes"], dtype=np.float32), names=np.array(names), signs=signs,
+                                    step=prep.S2DPreprocess(self.cfg, object_store=objects.get)))
+        self.points, self.dense_points, self.recon_points = [], [], []
+
+    def prepare(self):
+        """one pass of the data step over every frame: fills points / dense_points / recon_points and the padded ground truth"""
+        from . import targets as _targets
+        self.points, self.dense_points, self.recon_points = [], [], []
+        gt_b, gt_c = [], []
+        for f in self.frames:
+            res = dict(type="WaymoDataset", lidar=dict(points=f["points"].clone(), annotations=dict(boxes=f["boxes"].copy(), names=f["names"])))
+            info = dict(gt_boxes=f["boxes"], gt_names=f["names"], gt_signs=f["signs"])
+            res, _ = f["step"](res, info)
+            lidar = res["lidar"]
+            self.points.append(lidar["points"]); self.dense_points.append(lidar["dense_points"])
+            self.recon_points.append(lidar["reconstruction_points"])
+            boxes, classes = lidar["annotations"]["gt_boxes"], lidar["annotations"]["gt_classes"]
+            # AssignLabel regroups a task's objects class by class (preprocess.py:506-530)
+            order = np.concatenate([np.where(classes == c)[0] for c in range(1, len(self.cfg["class_names"]) + 1)])
+            gt_b.append(boxes[order]); gt_c.append(classes[order])
+        self.gt_boxes, self.gt_classes = _targets.pad_boxes(gt_b, gt_c, self.device)
+
+    def example(self):
+        self.prepare()
+        return super().example()
+
+
 NUSC_TRAIN_MAX_VOXELS = 120000   # configs/nusc/voxelnet/nusc_centerpoint_voxelnet_0075voxel_dcn.py: voxel_generator.max_voxel_num[0]
 # the scene generator's three kinds of objects spread over the ten nuScenes classes (waymo_configs.NUSC_TASKS order, 1-based)
 _NUSC_CLASSES_OF = {1: (1, 2, 3, 4, 5, 6), 2: (9, 10), 3: (7, 8)}

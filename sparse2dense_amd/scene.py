@@ -160,6 +160,33 @@ def make_distill_points(scene, seed=1, n_extra=20000):
     return np.ascontiguousarray(dense), np.ascontiguousarray(recon)
 
 
+WAYMO_CLASS_NAMES = ("VEHICLE", "PEDESTRIAN", "CYCLIST")   # gt_classes 1, 2, 3 of make_scene
+
+
+def make_object_clouds(scene, seed=1, n_total=20000, stored_fraction=0.8):
+    """Stand-in for the per-object store of completed clouds (`get_obj` on data/waymo/train/gt/<object>.pkl, preprocess.py:88-89): for
+    `stored_fraction` of the scene's boxes a cloud on the box surface in the OBJECT's frame, None for the others.  That frame is the
+    one `Preprocess` rotates by pi/2 + yaw: x runs along the box's second size column, y along its first.  Returns a list with one
+    [P_j, 5] fp32 array or None per box; about n_total rows in all."""
+    rs = np.random.RandomState(seed)
+    boxes = scene["gt_boxes"]
+    m = boxes.shape[0]
+    stored = rs.uniform(0, 1, m) < stored_fraction
+    per = max(int(n_total / max(stored.sum(), 1)), 1)
+    out = []
+    for j in range(m):
+        if not stored[j]:
+            out.append(None)
+            continue
+        k = max(int(per * rs.uniform(0.5, 1.5)), 1)
+        u = rs.uniform(-0.5, 0.5, (k, 3))
+        face = rs.randint(0, 3, k)
+        u[np.arange(k), face] = np.sign(u[np.arange(k), face]) * 0.5
+        local = u * boxes[j, [4, 3, 5]] * 0.98
+        out.append(np.concatenate([local, np.tanh(rs.uniform(0, 1.5, (k, 1))), rs.uniform(0, 1, (k, 1))], 1).astype(np.float32))
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # CenterPoint targets (AssignLabel, preprocess.py:553-624; center_utils.py:18-64)
 # ----------------------------------------------------------------------------------------------
