@@ -203,6 +203,11 @@ def _floats(values):
     return (ctypes.c_float * len(values))(*[float(v) for v in values])
 
 
+def _ws(nbytes, device):
+    """caller-owned scratch of one entry: a plain allocation of exactly the queried size (the seam tests/ws_guard.py replaces)"""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def assign_anchor_targets(gt_boxes, gt_classes, cfg, grid_xy=(1504, 1504)):
     """gt_boxes f32[B,K,7] (x,y,z,w,l,h,r; a 9-wide tensor with the velocities in columns 6:8 is accepted and narrowed) cuda,
     gt_classes i32[B,K] cuda (0 = padding), cfg = the config's `assigner` dictionary -> the example fields of AssignTarget after
@@ -224,7 +229,7 @@ def assign_anchor_targets(gt_boxes, gt_classes, cfg, grid_xy=(1504, 1504)):
     labels = torch.empty((b, a), dtype=torch.int32, device=dev)
     reg_targets = torch.empty((b, a, 7), dtype=torch.float32, device=dev)
     reg_weights = torch.empty((b, a), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(int(lib.s2d_anchor_assign_workspace_bytes(b, k)), 256), dtype=torch.uint8, device=dev)
+    ws = _ws(max(int(lib.s2d_anchor_assign_workspace_bytes(b, k)), 256), dev)
     _lib.check(lib.s2d_anchor_assign(gt_boxes.data_ptr(), gt_classes.data_ptr(), b, k, anchors.data_ptr(), a, asg.num_classes, asg.rotations,
                                      _floats(asg.matched), _floats(asg.unmatched), labels.data_ptr(), reg_targets.data_ptr(),
                                      reg_weights.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "s2d_anchor_assign")
@@ -291,7 +296,7 @@ class AnchorLossFn(torch.autograd.Function):
         dev = box_preds.device
         res = torch.empty(15, dtype=torch.float32, device=dev)
         norm = torch.empty(b, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(lib.s2d_anchor_loss_workspace_bytes(b)), dtype=torch.uint8, device=dev)
+        ws = _ws(lib.s2d_anchor_loss_workspace_bytes(b), dev)
         cparams = _floats(params)
         _lib.check(lib.s2d_anchor_loss_fwd(box_preds.data_ptr(), cls_preds.data_ptr(), dir_preds.data_ptr(), labels.data_ptr(),
                                            reg_targets.data_ptr(), anchors.data_ptr(), b, a, c, cparams, res.data_ptr(), norm.data_ptr(),

@@ -860,7 +860,8 @@ WS_PRIVATE = False   # set by graphed.GraphedSegment while it captures: a HIP gr
 
 def _ws(nbytes, device):
     """reduction workspace: one grow-only buffer per device and stream.  Every user writes it before reading it inside
-    one entry point, and launches on a stream are ordered, so consecutive calls can share it."""
+    one entry point, and launches on a stream are ordered, so consecutive calls can share it.  (Held by
+    tests/test_workspace_discipline_gpu.py: every user runs on exact-size, poisoned, guarded buffers - tests/ws_guard.py.)"""
     if WS_PRIVATE:   # graph capture: a plain allocation from the graph's memory pool, owned by the graph
         return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
     key = (device.index, _stream())

@@ -338,8 +338,7 @@ class _ConvT3dFn(torch.autograd.Function):
                 check(lib.s2d_convt3d_mfma_wgrad(_ptr(x), _ptr(dout), n, cin, cout, d, h, w, _ptr(dw), _ptr(ws), ws.numel(), _stream()),
                       "s2d_convt3d_mfma_wgrad")
             elif cin <= 32 and cout <= 32:
-                ws = torch.empty(max(lib.s2d_convt3d_k4s2p1_wgrad_workspace_bytes(n, cin, cout, d, h, w), 256),
-                                 dtype=torch.uint8, device=x.device)
+                ws = _ws(lib.s2d_convt3d_k4s2p1_wgrad_workspace_bytes(n, cin, cout, d, h, w), x.device)
                 check(lib.s2d_convt3d_k4s2p1_wgrad_f32(_ptr(x), _ptr(dout), n, cin, cout, d, h, w, _ptr(dw), _ptr(ws),
                                                        ws.numel(), _stream()), "s2d_convt3d_k4s2p1_wgrad_f32")
             else:   # wide layers: 64 plain GEMMs over the positions (hipBLASLt)

@@ -9,6 +9,11 @@ def _stream(dev):
     return torch._C._cuda_getCurrentRawStream(dev.index)
 
 
+def _ws(nbytes, device):
+    """caller-owned scratch of one entry: a plain allocation of exactly the queried size (the seam tests/ws_guard.py replaces)"""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def boxes_iou_bev(boxes_a, boxes_b):
     """[N,7] x [M,7] (x,y,z,dx,dy,dz,heading) cuda fp32 -> IoU matrix [N,M]"""
     if not boxes_a.is_cuda:
@@ -35,7 +40,7 @@ def rotate_nms(boxes, scores, thresh, pre_maxsize=None, post_max_size=None):
     b = boxes[order].float().contiguous()
     keep = torch.empty(n, dtype=torch.int64, device=b.device)
     n_keep = torch.empty(1, dtype=torch.int32, device=b.device)
-    ws = torch.empty(lib.s2d_nms_workspace_bytes(n), dtype=torch.uint8, device=b.device)
+    ws = _ws(lib.s2d_nms_workspace_bytes(n), b.device)
     max_keep = n if post_max_size is None else min(n, int(post_max_size))
     _lib.check(lib.s2d_nms_rotated_bev(b.data_ptr(), n, float(thresh), max_keep, keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(),
                                        _stream(b.device)), "s2d_nms_rotated_bev")
@@ -56,7 +61,7 @@ def circle_nms(centers_xy, scores, min_radius, post_max_size=83):
     xy = centers_xy[order].float().contiguous()
     keep = torch.empty(n, dtype=torch.int64, device=xy.device)
     n_keep = torch.empty(1, dtype=torch.int32, device=xy.device)
-    ws = torch.empty(lib.s2d_nms_workspace_bytes(n), dtype=torch.uint8, device=xy.device)
+    ws = _ws(lib.s2d_nms_workspace_bytes(n), xy.device)
     max_keep = n if post_max_size is None else min(n, int(post_max_size))
     _lib.check(lib.s2d_nms_circle(xy.data_ptr(), n, float(min_radius), max_keep, keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _stream(xy.device)), "s2d_nms_circle")
@@ -78,7 +83,7 @@ def _nms_batched(entry, what, rows, segments, counts, thresh, post_max_size, n_k
     n_keep = torch.empty((segs,), dtype=torch.int32, device=dev)
     if segs == 0:
         return keep, (n_keep if n_keep_on_device else [])
-    ws = torch.empty(lib.s2d_nms_batched_workspace_bytes(total, max_count), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.s2d_nms_batched_workspace_bytes(total, max_count), dev)
     _lib.check(getattr(lib, entry)(rows.data_ptr(), rows.shape[1] if rows.dim() == 2 else 0, segments[0].data_ptr(), segments[1].data_ptr(), segs,
                                    max_count, total, thresh, max_keep, keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(),
                                    _stream(dev)), entry)

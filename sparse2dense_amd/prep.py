@@ -167,11 +167,16 @@ def _stream(dev):
     return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
 
 
+def _ws(nbytes, device):
+    """caller-owned scratch of one entry: a plain allocation of exactly the queried size (the seam tests/ws_guard.py replaces)"""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def _workspace(lib, n, m, p, dev):
     size = lib.s2d_prep_workspace_bytes(n, m, p)
     if size == 0:
         raise _lib.S2DError(f"prep: {n} points, {m} boxes, {p} stored rows is outside the supported sizes")
-    return torch.empty(size, dtype=torch.uint8, device=dev)
+    return _ws(size, dev)
 
 
 def _inside_device(points, boxes, want_mask, want_counts):

@@ -29,6 +29,11 @@ import numpy as np
 import torch
 
 
+def _ws(nbytes, device):
+    """scratch of the gradient-norm reduction: a plain allocation of exactly the queried size (the seam tests/ws_guard.py replaces)"""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def annealing_cos(start, end, pct):
     """cosine anneal from `start` to `end` as pct goes 0 -> 1 (learning_schedules_fastai.py:67-71)"""
     return end + (start - end) / 2 * (math.cos(math.pi * pct) + 1)
@@ -282,7 +287,7 @@ class OneCycleAdam:
         dev, stream = ps[0].device, _stream()
         clip = None
         if not math.isinf(max_norm):
-            ws = torch.empty(c["ws_floats"], dtype=torch.float32, device=dev)
+            ws = _ws(4 * c["ws_floats"], dev)   # fp32 partial sums
             written = 0
             for lo, hi, numel_chunk in c["norm_chunks"]:
                 w = ctypes.c_int(0)
