@@ -1315,6 +1315,38 @@ int s2d_prep_global_noise(float *cloud0, int64_t rows0, float *cloud1, int64_t r
                           s2d_stream_t stream);
 int s2d_prep_gather_rows(const float *src, int64_t rows, int ncols, const int64_t *perm, float *dst, s2d_stream_t stream);
 
+/*
+ * GT-database sampler of the training step (csrc/prep.hip, csrc/box_collision.h; det3d/core/sampler/sample_ops.py:134-359 and
+ * box_collision_test of det3d/core/sampler/preprocess.py:922-1005, its `is True / is False` read by value: containment collides).
+ *
+ * s2d_prep_box_collision: out [n][k] bytes, out[i][j] = box_collision_test(corners, qcorners)[i][j]; corners [n][4][2] fp32.
+ *
+ * s2d_prep_gt_select (three launches): boxes [num_avoid + num_cand][box_dim], the frame's boxes first, then every group's candidates in
+ * group order; group_ends HOST [num_groups], the exclusive end of each group's candidates; cand_meta DEVICE int32 [num_cand][5] = the
+ * candidate's sweep rows [lo, hi) in src_points, its completed cloud's rows [lo, hi) in cc_points (empty: none; both clamped on the
+ * device) and its kind (1 VEHICLE).  Candidates are walked in order; one is rejected when it collides with a frame box, an accepted
+ * candidate, or a candidate of its own group that has not been rejected (later ones included).  header DEVICE int32 [2 + num_cand] =
+ * accepted sweep rows, accepted reconstruction rows, accept[num_cand]: the step's one host read.  The reconstruction block of a candidate is
+ * its completed cloud (VEHICLE: the side of y with strictly more rows, then its mirror image), rotated by pi / 2 + yaw, translated, and only
+ * the rows strictly inside its own box; without a completed cloud, its translated sweep rows.
+ * Limits: num_avoid + num_cand <= S2D_PREP_MAX_BOXES, 1 <= num_cand <= S2D_PREP_MAX_CANDIDATES, num_groups <= S2D_PREP_MAX_GROUPS;
+ * s2d_prep_gt_scratch_bytes returns 0 outside them.
+ *
+ * s2d_prep_gt_paste (one launch, same ws and header): the accepted candidates' sweep rows with the box centre added to columns 0-2 into rows
+ * 0 .. sampled_rows - 1 of points_out and of dense_out (may be NULL), their reconstruction blocks into rows 0 .. recon_rows - 1 of recon_out
+ * (may be NULL with recon_rows 0).  Never writes past sampled_rows / recon_rows.
+ */
+#define S2D_PREP_MAX_CANDIDATES 128
+#define S2D_PREP_MAX_GROUPS 16
+size_t s2d_prep_gt_scratch_bytes(int num_avoid, int num_cand);
+int s2d_prep_box_collision(const float *corners, int n, const float *qcorners, int k, uint8_t *out, s2d_stream_t stream);
+int s2d_prep_gt_select(const float *boxes, int num_avoid, int num_cand, int box_dim, const int32_t *group_ends, int num_groups,
+                       const int32_t *cand_meta, const float *cc_points, int64_t src_rows, int64_t cc_rows, int ncols, void *ws, size_t ws_bytes,
+                       int32_t *header, s2d_stream_t stream);
+int s2d_prep_gt_paste(int num_cand, int ncols, const int32_t *cand_meta, const float *src_points, int64_t src_rows, const float *cc_points,
+                      int64_t cc_rows, const void *ws, size_t ws_bytes, const int32_t *header, float *points_out, float *dense_out,
+                      int64_t sampled_rows, float *recon_out, int64_t recon_rows, s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

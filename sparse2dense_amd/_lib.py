@@ -481,6 +481,15 @@ SIGNATURES = {
     "s2d_prep_global_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] * 3 + [ctypes.c_int] +
                               [ctypes.c_double] * 3 + [ctypes.c_void_p]),
     "s2d_prep_gather_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # GT-database sampler: collision matrix, select (select + count + segments), paste (csrc/prep.hip, csrc/box_collision.h)
+    "s2d_prep_gt_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "s2d_prep_box_collision": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_prep_gt_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_prep_gt_paste": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 // Counting and filling evaluate the same device function on the same operands, so they agree on every membership; all counts are integers
 // and there is no floating-point atomic: two calls give the same bits.
 #include "s2d_common.h"
+#include "box_collision.h"
 #include "scan.h"
 
 namespace s2d {
@@ -432,6 +433,267 @@ int prep_stage(const float *boxes, int m, int box_dim, const int8_t *kinds, cons
     return S2D_OK;
 }
 
+// ---- GT-database sampler (det3d/core/sampler/sample_ops.py:134-359) -----------------------------------------------------------------------------
+// gt_select_kernel    ONE workgroup for all groups of a frame: corners and stand-up boxes of the M avoid boxes and the S candidates in LDS, the
+//                     S x (M + S) bit matrix of box_collision_test in LDS (a wave owns a row word: one pair per lane, the ballot is the word),
+//                     then one wave walks groups and candidates in order against the alive mask (lane w holds word w), then the accepted
+//                     blocks' exclusive row offsets.
+// gt_count_kernel     one workgroup per accepted candidate: the rows of its completed cloud per side of y and strictly inside its OWN box
+//                     (original and mirror image), the VEHICLE side, the length of its reconstruction block.
+// gt_segments_kernel  one workgroup: exclusive prefix of the reconstruction block lengths, their total to the header.
+// gt_paste_kernel     one workgroup per accepted candidate: its sweep rows plus the box centre to the front of the new sweep and dense cloud,
+//                     its reconstruction block (order-preserving, kept side first, then the mirror image) to the front of the new
+//                     reconstruction cloud.
+constexpr int GT_MAX_CAND = S2D_PREP_MAX_CANDIDATES;
+constexpr int GT_MAX_GROUPS = S2D_PREP_MAX_GROUPS;
+constexpr int GT_WORDS = PREP_MAX_BOXES / 64;
+constexpr int GT_META = 5;   // per candidate: sweep rows lo, hi; completed cloud rows lo, hi; kind
+constexpr int GT_SEG = 6;    // per candidate: sweep base, reconstruction base, reconstruction length, kept rows, kept rows inside, side y > 0
+
+struct GtGroups {
+    int end[GT_MAX_GROUPS];   // exclusive end of each group's candidates
+    int n;
+};
+
+struct GtWs {
+    float *table;   // [S][PREP_BOX_F]
+    int *range;     // [S][4]  sanitised meta ranges
+    int *seg;       // [S][GT_SEG]
+    size_t bytes;
+};
+
+GtWs gt_carve(void *ws, int s) {
+    Carver c(ws);
+    GtWs w;
+    w.table = c.take<float>((size_t)s * PREP_BOX_F);
+    w.range = c.take<int>((size_t)s * 4);
+    w.seg = c.take<int>((size_t)s * GT_SEG);
+    w.bytes = c.total();
+    return w;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void prep_collision_kernel(const float *corners, int n, const float *qcorners, int k, uint8_t *out) {
+    const int64_t e = (int64_t)blockIdx.x * PREP_THREADS + threadIdx.x;
+    if (e >= (int64_t)n * k) return;
+    const int i = (int)(e / k), j = (int)(e - (int64_t)i * k);
+    float b[8], q[8], bs[4], qs[4];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) b[t] = corners[(size_t)i * 8 + t], q[t] = qcorners[(size_t)j * 8 + t];
+    standup_of(b, bs);
+    standup_of(q, qs);
+    out[e] = box_pair_collides(b, bs, q, qs) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void gt_select_kernel(const float *boxes, int m, int s, int box_dim, GtGroups groups, const int32_t *meta,
+                                                                  int64_t src_rows, int64_t cc_rows, float *table, int *range, int *seg,
+                                                                  int32_t *header) {
+    __shared__ float corner[PREP_MAX_BOXES * 8];
+    __shared__ float standup[PREP_MAX_BOXES * 4];
+    __shared__ unsigned long long bits[GT_MAX_CAND * GT_WORDS];
+    __shared__ int accept[GT_MAX_CAND];
+    __shared__ int lds[4];
+    const int total = m + s, words = (total + 63) >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int j = threadIdx.x; j < total; j += PREP_THREADS) {
+        const float *b = boxes + (size_t)j * box_dim;
+        bev_corners_of(b, box_dim, corner + 8 * j, standup + 4 * j);
+        if (j >= m) {   // the candidate's staged box (inside test, rotation by pi/2 + yaw) and its sanitised row ranges
+            const int i = j - m;
+            const double r = (double)b[box_dim - 1];
+            float *t = table + (size_t)i * PREP_BOX_F;
+            t[0] = b[0], t[1] = b[1], t[2] = b[2];
+            t[3] = b[3] * 0.5f, t[4] = b[4] * 0.5f, t[5] = b[5] * 0.5f;
+            t[6] = (float)cos(r), t[7] = (float)sin(r);
+            t[8] = (float)cos(1.5707963267948966 + r), t[9] = (float)sin(1.5707963267948966 + r);
+            const int32_t *mt = meta + (size_t)i * GT_META;
+            const int lo = (int)min((int64_t)max(mt[0], 0), src_rows), hi = (int)min((int64_t)max(mt[1], lo), src_rows);
+            const int clo = (int)min((int64_t)max(mt[2], 0), cc_rows), chi = (int)min((int64_t)max(mt[3], clo), cc_rows);
+            range[4 * i] = lo, range[4 * i + 1] = hi, range[4 * i + 2] = clo, range[4 * i + 3] = chi;
+        }
+    }
+    __syncthreads();
+    // bits[i][w]: row i = candidate i as `boxes`, column j = box j as `qboxes`; the diagonal is clear
+    for (int item = wave; item < s * words; item += PREP_WAVES) {
+        const int i = item / words, w = item - i * words;
+        const int j = w * 64 + lane;
+        bool hit = false;
+        if (j < total && j != m + i) hit = box_pair_collides(corner + 8 * (m + i), standup + 4 * (m + i), corner + 8 * j, standup + 4 * j);
+        const unsigned long long word = __ballot(hit);
+        if (lane == 0) bits[i * GT_WORDS + w] = word;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        // lane w < words holds word w of the alive mask: the avoid boxes always, a group's candidates from its start until rejected
+        unsigned long long alive = 0ull;
+        if (lane < words) {
+            const int lo = lane * 64;
+            if (m >= lo + 64) alive = ~0ull;
+            else if (m > lo) alive = (1ull << (m - lo)) - 1ull;
+        }
+        int start = 0;
+        for (int g = 0; g < groups.n; ++g) {
+            const int end = min(max(groups.end[g], start), s);
+            if (lane < words) {
+                const int lo = lane * 64;
+                for (int i = start; i < end; ++i) {
+                    const int col = m + i - lo;
+                    if (col >= 0 && col < 64) alive |= 1ull << col;
+                }
+            }
+            for (int i = start; i < end; ++i) {
+                const unsigned long long row = lane < words ? bits[i * GT_WORDS + lane] & alive : 0ull;
+                const bool rejected = __ballot(row != 0ull) != 0ull;   // wave-uniform
+                if (rejected) {
+                    const int col = m + i - lane * 64;
+                    if (col >= 0 && col < 64) alive &= ~(1ull << col);
+                }
+                if (lane == 0) accept[i] = rejected ? 0 : 1;
+            }
+            start = end;
+        }
+        for (int i = start + lane; i < s; i += 64) accept[i] = 0;   // candidates beyond the last group belong to none
+    }
+    __syncthreads();
+    const int i = threadIdx.x;
+    const int ok = i < s ? accept[i] : 0;
+    const int rows = ok ? range[4 * i + 1] - range[4 * i] : 0;
+    int rows_total;
+    const int base = block_exclusive_scan(rows, &rows_total, lds);
+    if (i < s) {
+        seg[GT_SEG * i] = base;
+        header[2 + i] = ok;
+    }
+    if (i == 0) header[0] = rows_total;
+}
+
+// flag bits of one completed-cloud row against the candidate's own box: the sign of y, the image and the mirror image strictly inside
+__device__ __forceinline__ int gt_row_flags(const float *t, const float *row, float *out /*ox oy oz mx my*/) {
+    const float x = row[0], y = row[1], z = row[2];
+    const float c = t[8], s = t[9];
+    out[0] = (x * c + y * s) + t[0], out[1] = (x * -s + y * c) + t[1], out[2] = z + t[2];
+    const float my = -y;
+    out[3] = (x * c + my * s) + t[0], out[4] = (x * -s + my * c) + t[1];
+    int f = 0;
+    if (y > 0.f) f |= PREP_F_POS;
+    if (y < 0.f) f |= PREP_F_NEG;
+    if (prep_inside(t, out[0], out[1], out[2])) f |= PREP_F_IN;
+    if (prep_inside(t, out[3], out[4], out[2])) f |= PREP_F_IN_MIRROR;
+    return f;
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void gt_count_kernel(int s, int ncols, const int32_t *meta, const float *cc_points, const float *table,
+                                                                 const int *range, int *seg, const int32_t *header) {
+    __shared__ int cnt[PREP_OBJ_CNT];
+    __shared__ float t[PREP_BOX_F];
+    const int i = blockIdx.x;
+    int *sg = seg + GT_SEG * i;
+    const int lo = range[4 * i], hi = range[4 * i + 1], clo = range[4 * i + 2], chi = range[4 * i + 3];
+    if (!header[2 + i] || chi <= clo) {   // rejected: nothing; no completed cloud: the reconstruction block is the sampled rows
+        if (threadIdx.x == 0) sg[2] = header[2 + i] ? hi - lo : 0, sg[3] = 0, sg[4] = 0, sg[5] = 0;
+        return;
+    }
+    if (threadIdx.x < PREP_OBJ_CNT) cnt[threadIdx.x] = 0;
+    if (threadIdx.x < PREP_BOX_F) t[threadIdx.x] = table[(size_t)i * PREP_BOX_F + threadIdx.x];
+    __syncthreads();
+    int acc[PREP_OBJ_CNT - 1] = {0, 0, 0, 0, 0, 0, 0};
+    for (int q = clo + threadIdx.x; q < chi; q += PREP_THREADS) {
+        float o[5];
+        const int f = gt_row_flags(t, cc_points + (size_t)q * ncols, o);
+        const bool pos = f & PREP_F_POS, neg = f & PREP_F_NEG, in = f & PREP_F_IN, in_m = f & PREP_F_IN_MIRROR;
+        acc[0] += pos, acc[1] += neg;
+        acc[2] += pos && in, acc[3] += pos && in_m;
+        acc[4] += neg && in, acc[5] += neg && in_m;
+        acc[6] += in;
+    }
+#pragma unroll
+    for (int k = 0; k < PREP_OBJ_CNT - 1; ++k)
+        if (acc[k]) atomicAdd(&cnt[k], acc[k]);   // integer sums in LDS: the order does not matter
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (meta[(size_t)i * GT_META + 4] == 1) {   // VEHICLE: strictly more rows with y > 0 keeps that side, a tie keeps y < 0
+            const bool pos = cnt[0] > cnt[1];
+            sg[3] = pos ? cnt[0] : cnt[1];
+            sg[4] = pos ? cnt[2] : cnt[4];
+            sg[2] = sg[4] + (pos ? cnt[3] : cnt[5]);
+            sg[5] = pos;
+        } else {
+            sg[3] = chi - clo, sg[4] = cnt[6], sg[2] = cnt[6], sg[5] = 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void gt_segments_kernel(int s, int *seg, int32_t *header) {
+    __shared__ int lds[4];
+    const int i = threadIdx.x;
+    int total;
+    const int base = block_exclusive_scan(i < s ? seg[GT_SEG * i + 2] : 0, &total, lds);
+    if (i < s) seg[GT_SEG * i + 1] = base;
+    if (i == 0) header[1] = total;
+}
+
+__device__ __forceinline__ void gt_put_row(float *cloud, int row, int rows, int ncols, float x, float y, float z, const float *src) {
+    if (!cloud || row >= rows) return;
+    float *dst = cloud + (size_t)row * ncols;
+    dst[0] = x, dst[1] = y, dst[2] = z;
+    for (int e = 3; e < ncols; ++e) dst[e] = src[e];
+}
+
+__global__ __launch_bounds__(PREP_THREADS) void gt_paste_kernel(int s, int ncols, const int32_t *meta, const float *src_points, const float *cc_points,
+                                                                 const float *table, const int *range, const int *seg, const int32_t *header,
+                                                                 float *points_out, float *dense_out, int sampled_rows, float *recon_out,
+                                                                 int recon_rows) {
+    __shared__ int lds[4];
+    __shared__ float t[PREP_BOX_F];
+    const int i = blockIdx.x;
+    if (!header[2 + i]) return;
+    if (threadIdx.x < PREP_BOX_F) t[threadIdx.x] = table[(size_t)i * PREP_BOX_F + threadIdx.x];
+    __syncthreads();
+    const int lo = range[4 * i], hi = range[4 * i + 1], clo = range[4 * i + 2], chi = range[4 * i + 3];
+    const int *sg = seg + GT_SEG * i;
+    const int base = sg[0], recon0 = sg[1], kept_in_all = sg[4];
+    const bool own = chi <= clo;   // no completed cloud: the sampled rows are the reconstruction block too
+    for (int q = lo + threadIdx.x; q < hi; q += PREP_THREADS) {
+        const float *src = src_points + (size_t)q * ncols;
+        const float x = src[0] + t[0], y = src[1] + t[1], z = src[2] + t[2];
+        const int k = q - lo;
+        gt_put_row(points_out, base + k, sampled_rows, ncols, x, y, z, src);
+        gt_put_row(dense_out, base + k, sampled_rows, ncols, x, y, z, src);
+        if (own) gt_put_row(recon_out, recon0 + k, recon_rows, ncols, x, y, z, src);
+    }
+    if (own || !recon_out) return;
+    const bool vehicle = meta[(size_t)i * GT_META + 4] == 1;
+    const int side = sg[5] ? PREP_F_POS : PREP_F_NEG;
+    int run_in = 0, run_in_m = 0;
+    for (int b = clo; b < chi; b += PREP_THREADS) {   // (every thread takes every turn: the scan has barriers)
+        const int q = b + threadIdx.x;
+        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        const float *src = cc_points + (size_t)min(q, chi - 1) * ncols;
+        int f = 0;
+        bool keep = false;
+        if (q < chi) {
+            f = gt_row_flags(t, src, o);
+            keep = !vehicle || (f & side);
+        }
+        const bool in = keep && (f & PREP_F_IN), in_m = keep && vehicle && (f & PREP_F_IN_MIRROR);
+        const int packed = (int)in | ((int)in_m << 10);   // two counts of at most 256 each in one scan
+        int total;
+        const int ex = block_exclusive_scan(packed, &total, lds);
+        if (in) gt_put_row(recon_out, recon0 + run_in + (ex & 1023), recon_rows, ncols, o[0], o[1], o[2], src);
+        if (in_m) gt_put_row(recon_out, recon0 + kept_in_all + run_in_m + ((ex >> 10) & 1023), recon_rows, ncols, o[3], o[4], o[2], src);
+        run_in += total & 1023, run_in_m += (total >> 10) & 1023;
+    }
+}
+
+int gt_check_sizes(const char *what, int m, int s, int box_dim, int ncols, int64_t src_rows, int64_t cc_rows) {
+    S2D_CHECK_ARG(m >= 0 && s >= 1 && s <= GT_MAX_CAND, "%s: %d candidates (1..%d)", what, s, GT_MAX_CAND);
+    S2D_CHECK_ARG(m + s <= PREP_MAX_BOXES, "%s: %d avoid boxes + %d candidates (at most %d boxes)", what, m, s, PREP_MAX_BOXES);
+    S2D_CHECK_ARG(box_dim >= 7 && box_dim <= 16, "%s: box_dim %d (7..16: centre, size, ..., yaw last)", what, box_dim);
+    S2D_CHECK_ARG(ncols >= 3 && ncols <= 16, "%s: %d point columns (3..16)", what, ncols);
+    S2D_CHECK_ARG(src_rows >= 0 && src_rows <= S2D_PREP_MAX_POINTS && cc_rows >= 0 && cc_rows <= S2D_PREP_MAX_POINTS,
+                  "%s: store rows %lld / %lld (0..%d)", what, (long long)src_rows, (long long)cc_rows, S2D_PREP_MAX_POINTS);
+    return S2D_OK;
+}
+
 }  // namespace
 }  // namespace s2d
 
@@ -550,6 +812,68 @@ extern "C" int s2d_prep_gather_rows(const float *src, int64_t rows, int ncols, c
     S2D_CHECK_ARG(src && perm && dst && src != dst, "prep_gather_rows: null argument or in-place gather");
     hipLaunchKernelGGL(prep_gather_kernel, dim3((unsigned)ceil_div(rows * ncols, PREP_THREADS)), dim3(PREP_THREADS), 0, (hipStream_t)stream, src, rows,
                        ncols, perm, dst);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
+}
+
+extern "C" size_t s2d_prep_gt_scratch_bytes(int num_avoid, int num_cand) {
+    if (num_avoid < 0 || num_cand < 1 || num_cand > GT_MAX_CAND || num_avoid + num_cand > PREP_MAX_BOXES) return 0;
+    return gt_carve(nullptr, num_cand).bytes + 256;
+}
+
+extern "C" int s2d_prep_box_collision(const float *corners, int n, const float *qcorners, int k, uint8_t *out, s2d_stream_t stream) {
+    S2D_CHECK_ARG(n >= 0 && k >= 0 && (int64_t)n * k <= (int64_t)1 << 24, "prep_box_collision: %d x %d boxes (at most 2^24 pairs)", n, k);
+    if (n == 0 || k == 0) return S2D_OK;
+    S2D_CHECK_ARG(corners && qcorners && out, "prep_box_collision: null corners or output");
+    hipLaunchKernelGGL(prep_collision_kernel, dim3((unsigned)ceil_div((int64_t)n * k, PREP_THREADS)), dim3(PREP_THREADS), 0, (hipStream_t)stream,
+                       corners, n, qcorners, k, out);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
+}
+
+extern "C" int s2d_prep_gt_select(const float *boxes, int num_avoid, int num_cand, int box_dim, const int32_t *group_ends, int num_groups,
+                                  const int32_t *cand_meta, const float *cc_points, int64_t src_rows, int64_t cc_rows, int ncols, void *ws,
+                                  size_t ws_bytes, int32_t *header, s2d_stream_t stream) {
+    if (int rc = gt_check_sizes("prep_gt_select", num_avoid, num_cand, box_dim, ncols, src_rows, cc_rows)) return rc;
+    S2D_CHECK_ARG(num_groups >= 1 && num_groups <= GT_MAX_GROUPS && group_ends, "prep_gt_select: %d groups (1..%d)", num_groups, GT_MAX_GROUPS);
+    GtGroups groups;
+    groups.n = num_groups;
+    for (int g = 0; g < GT_MAX_GROUPS; ++g) groups.end[g] = g < num_groups ? group_ends[g] : num_cand;
+    for (int g = 0; g < num_groups; ++g)
+        S2D_CHECK_ARG(groups.end[g] >= (g ? groups.end[g - 1] : 0) && groups.end[g] <= num_cand, "prep_gt_select: group ends must not decrease (0..%d)",
+                      num_cand);
+    S2D_CHECK_ARG(boxes && cand_meta && header, "prep_gt_select: null boxes, candidate table or header");
+    S2D_CHECK_ARG(cc_rows == 0 || cc_points, "prep_gt_select: null completed clouds");
+    const GtWs w = gt_carve(ws, num_cand);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("prep_gt_select: workspace %zu bytes, %zu needed", ws_bytes, w.bytes);
+        return S2D_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(gt_select_kernel, dim3(1), dim3(PREP_THREADS), 0, st, boxes, num_avoid, num_cand, box_dim, groups, cand_meta, src_rows, cc_rows,
+                       w.table, w.range, w.seg, header);
+    hipLaunchKernelGGL(gt_count_kernel, dim3(num_cand), dim3(PREP_THREADS), 0, st, num_cand, ncols, cand_meta, cc_points, w.table, w.range, w.seg, header);
+    hipLaunchKernelGGL(gt_segments_kernel, dim3(1), dim3(PREP_THREADS), 0, st, num_cand, w.seg, header);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
+}
+
+extern "C" int s2d_prep_gt_paste(int num_cand, int ncols, const int32_t *cand_meta, const float *src_points, int64_t src_rows, const float *cc_points,
+                                 int64_t cc_rows, const void *ws, size_t ws_bytes, const int32_t *header, float *points_out, float *dense_out,
+                                 int64_t sampled_rows, float *recon_out, int64_t recon_rows, s2d_stream_t stream) {
+    if (int rc = gt_check_sizes("prep_gt_paste", 0, num_cand, 7, ncols, src_rows, cc_rows)) return rc;
+    S2D_CHECK_ARG(sampled_rows >= 0 && recon_rows >= 0 && sampled_rows <= S2D_PREP_MAX_POINTS && recon_rows <= S2D_PREP_MAX_POINTS,
+                  "prep_gt_paste: output rows %lld / %lld", (long long)sampled_rows, (long long)recon_rows);
+    S2D_CHECK_ARG(cand_meta && header, "prep_gt_paste: null candidate table or header");
+    S2D_CHECK_ARG((src_rows == 0 || src_points) && (cc_rows == 0 || cc_points), "prep_gt_paste: null stored rows");
+    S2D_CHECK_ARG(sampled_rows == 0 || points_out, "prep_gt_paste: null output");
+    const GtWs w = gt_carve(const_cast<void *>(ws), num_cand);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("prep_gt_paste: workspace %zu bytes, %zu needed", ws_bytes, w.bytes);
+        return S2D_ERR_WORKSPACE;
+    }
+    hipLaunchKernelGGL(gt_paste_kernel, dim3(num_cand), dim3(PREP_THREADS), 0, (hipStream_t)stream, num_cand, ncols, cand_meta, src_points, cc_points,
+                       w.table, w.range, w.seg, header, points_out, dense_out, (int)sampled_rows, recon_rows ? recon_out : nullptr, (int)recon_rows);
     S2D_LAUNCH_CHECK();
     return S2D_OK;
 }

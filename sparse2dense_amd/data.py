@@ -110,13 +110,14 @@ class PreparedFrames(SyntheticFrames):
     frames: a list of dictionaries with `points` [N, 5], `gt_boxes` [M, 9] (velocity columns, yaw last: what the target assignment takes), `gt_names` [M] (the kinds follow from them:
     VEHICLE, SIGN, other) and `objects`, one [P_j, 5] completed cloud in the object's own frame or None per box.  cfg: the `Preprocess`
     keys of the reference's training config (mode "train", distillation True, db_sampler None); the default is the Waymo distillation
-    config's noise with three classes."""
+    config's noise with three classes.  db_sampler: a built `prep.GTSampler` (9-column boxes, 5-column rows; `.resident(device)` keeps its
+    rows on the device) handed to every frame's step - one sampler, so its draws run on through the frames in order."""
 
     DEFAULT_CFG = dict(mode="train", shuffle_points=True, distillation=True, global_rot_noise=[-0.78539816, 0.78539816],
                        global_scale_noise=[0.95, 1.05], global_translate_std=0.5, db_sampler=None, class_names=list(scene.WAYMO_CLASS_NAMES),
                        no_augmentation=False)
 
-    def __init__(self, frames, cfg=None, device="cuda", anchor_targets=None):
+    def __init__(self, frames, cfg=None, device="cuda", anchor_targets=None, db_sampler=None):
         from . import prep
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -137,7 +138,7 @@ class PreparedFrames(SyntheticFrames):
                        for s, g in zip(signs, f["objects"]) if g is not None and len(g)}
             self.frames.append(dict(points=torch.from_numpy(np.ascontiguousarray(f["points"], dtype=np.float32)).to(self.device),
                                     boxes=np.ascontiguousarray(f["gt_boxes"], dtype=np.float32), names=np.array(names), signs=signs,
-                                    step=prep.S2DPreprocess(self.cfg, object_store=objects.get)))
+                                    step=prep.S2DPreprocess(self.cfg, object_store=objects.get, db_sampler=db_sampler)))
         self.points, self.dense_points, self.recon_points = [], [], []
 
     def prepare(self):
