@@ -1347,6 +1347,40 @@ int s2d_prep_gt_paste(int num_cand, int ncols, const int32_t *cand_meta, const f
                       int64_t cc_rows, const void *ws, size_t ws_bytes, const int32_t *header, float *points_out, float *dense_out,
                       int64_t sampled_rows, float *recon_out, int64_t recon_rows, s2d_stream_t stream);
 
+/* ---- center-based multi-object tracker (csrc/tracking.hip): PubTracker.step_centertrack of the reference's tools/nusc_tracking and
+ * tools/waymo_tracking behind transform_box, one workgroup per segment (sequence), every segment in ONE launch, nothing for the host to read.
+ *
+ * boxes [rows][9] fp32 in the lidar frame (centre 0-2, velocity 6-7), labels int64 [rows], scores fp32 [rows].  segments DEVICE
+ * [num_segments]: pose = the first three rows of the 4x4 lidar-to-global matrix (row major), time_lag = this frame's timestamp minus the
+ * previous one's, first != 0: the segment is reset before the step (tracks cleared, id_count 0), skip != 0: the segment's state is copied
+ * to the new buffers bit for bit and its rows get tracking_id -1, [row_lo, row_hi) the segment's rows (clamped to 0 .. rows; at most
+ * S2D_TRACK_MAX_DETS are used).  label_table DEVICE [num_labels]: the tracking class of a detection label (0 .. 126, or negative: the
+ * label is not tracked) and its max_diff in metres.  score_thresh < 0: every unmatched detection starts a track (the nuScenes rule);
+ * otherwise only those with score > score_thresh (fp32), the others are dropped (the Waymo rule).
+ *
+ * State per segment, capacity S2D_TRACK_MAX_TRACKS, read from the *_old buffers and written to the *_new ones (different buffers):
+ * ct, tracking double [S][cap][2], meta int32 [S][cap][4] = class, id, age, active, head int32 [S][2] = count, id_count.  The new list
+ * holds the matched detections in detection order (the track's id, age 1, active + 1), the unmatched ones (id = ++id_count, age 1, active
+ * 1), then the unmatched old tracks with age < max_age in track order (age + 1, active 0, ct - tracking).  A segment without rows clears
+ * its tracks and keeps id_count; with rows that are all filtered every track is unmatched and ages (the reference raises there).
+ * tracking_id, active int32 [rows] in detection order: -1 / 0 for filtered or dropped rows. */
+#define S2D_TRACK_MAX_SEGMENTS 64
+#define S2D_TRACK_MAX_DETS 1024
+#define S2D_TRACK_MAX_TRACKS 4096
+typedef struct {
+    double pose[12];
+    double time_lag;
+    int32_t first, skip, row_lo, row_hi;
+} s2d_track_segment;
+typedef struct {
+    int32_t cls;
+    float max_diff;
+} s2d_track_label;
+int s2d_track_step(const float *boxes, const int64_t *labels, const float *scores, int64_t rows, int num_segments,
+                   const s2d_track_segment *segments, const s2d_track_label *label_table, int num_labels, int max_age, float score_thresh,
+                   const double *ct_old, const double *tracking_old, const int32_t *meta_old, const int32_t *head_old, double *ct_new,
+                   double *tracking_new, int32_t *meta_new, int32_t *head_new, int32_t *tracking_id, int32_t *active, s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -490,6 +490,9 @@ SIGNATURES = {
     "s2d_prep_gt_paste": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    # center-based tracker: every segment's step in one launch (csrc/tracking.hip)
+    "s2d_track_step": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_float] + [ctypes.c_void_p] * 10 + [ctypes.c_void_p]),
 }
 
 _lib = None
