@@ -1,6 +1,7 @@
 """Per-shape timing of the bf16-storage sparse-conv gather kernels on the bench scene's REAL rulebooks (150 k points x 4 frames):
 every SubM stage (forward = data gradient shape), the strided convs (forward over nbr_out, data gradient over nbr_in) and the
-weight gradients.  One process = one kernel variant (S2D_S16_KERNEL / S2D_RG_PLAN are read once by the library), so A/B runs are
+weight gradients.  One process = one kernel variant (S2D_S16_KERNEL is read once by the library; S2D_RG_PLAN / S2D_S16_PLAN are read on
+every launch - tests/test_spconv_plans_gpu.py runs every plan they select - but this tool keeps to one per process), so A/B runs are
 separate invocations:
 
     S2D_S16_KERNEL=lds python tools/spconv_kernel_bench.py
