@@ -1634,6 +1634,7 @@ extern "C" int s2d_convt3d_mfma_fwd_stats_y16_norm(const float *in, const float 
                                                    int cin, int cout, int d, int h, int w, void *out_bf16, float *stats_partial,
                                                    s2d_stream_t stream) {
     S2D_CHECK_ARG(in_scale_shift, "convt3d_mfma_fwd_stats_y16_norm: null scale / shift");
+    if (!s2d_convt3d_mfma_norm_supported(cin, cout, d, h, w)) return S2D_ERR_UNSUPPORTED;   // like s2d_convt3d_mfma_wgrad_d16_norm: one predicate for the fold
     return ct_fwd_launch<__bf16>(in, packed, bias, batch, cin, cout, d, h, w, (__bf16 *)out_bf16, stats_partial, stream, in_scale_shift);
 }
 
@@ -1643,7 +1644,7 @@ extern "C" int s2d_convt3d_mfma_fwd_stats_y16_norm_x16(const void *in_bf16, cons
                                                        int batch, int cin, int cout, int d, int h, int w, void *out_bf16, float *stats_partial,
                                                        s2d_stream_t stream) {
     S2D_CHECK_ARG(in_scale_shift, "convt3d_mfma_fwd_stats_y16_norm_x16: null scale / shift");
-    if (!ct_fwd_zslide(cin)) return S2D_ERR_UNSUPPORTED;
+    if (!s2d_convt3d_mfma_x16_supported(cin, cout, d, h, w)) return S2D_ERR_UNSUPPORTED;   // includes the z-sliding plan (S2D_CT_ZSLIDE != 0)
     return ct_fwd_launch<__bf16, __bf16>((const __bf16 *)in_bf16, packed, bias, batch, cin, cout, d, h, w, (__bf16 *)out_bf16, stats_partial, stream,
                                          in_scale_shift);
 }
