@@ -1560,15 +1560,8 @@ extern "C" int s2d_convt3d_mfma_pack_weights(const float *weight, int cin, int c
 static int ct_fwd_rows(int cin) { return cin == 32 ? 1 : 4; }
 
 // r06: 16-channel inputs take the z-sliding kernel (a block = (n, 4 rows, x tile) for every z: each plane staged once per block instead of three
-// times); S2D_CT_ZSLIDE=0 keeps the per-z blocks for A/B runs
-static bool ct_fwd_zslide(int cin) {
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("S2D_CT_ZSLIDE");
-        on = e ? atoi(e) : 1;
-    }
-    return on && (cin == 16 || (cin == 32 && on == 2));   // S2D_CT_ZSLIDE=2: the 32-channel layer too (A/B)
-}
+// times: 457 us against 575 with per-z blocks); 32-channel inputs keep the per-z blocks (405 us against 521 with the z-sliding ring)
+static bool ct_fwd_zslide(int cin) { return cin == 16; }
 
 extern "C" int64_t s2d_convt3d_mfma_stats_tiles(int batch, int cin, int d, int h, int w) {
     const int yr = ct_fwd_rows(cin);
@@ -1597,9 +1590,7 @@ static int ct_fwd_launch(const TXI *in, const void *packed, const float *bias, i
     } else {
     if (ct_fwd_zslide(cin)) {
         const dim3 zgrid(xcd_grid((int64_t)batch * hg * xtiles)), zblk(256);
-        if (cin == 32 && nt == 2) hipLaunchKernelGGL((ct_fwd_zslide_kernel<32, 2, 1, TO>), zgrid, zblk, 0, st, in, wp, bias, s, xtiles, out, stats_partial, in_norm);
-        else if (cin == 32) hipLaunchKernelGGL((ct_fwd_zslide_kernel<32, 1, 1, TO>), zgrid, zblk, 0, st, in, wp, bias, s, xtiles, out, stats_partial, in_norm);
-        else if (nt == 2) hipLaunchKernelGGL((ct_fwd_zslide_kernel<16, 2, 4, TO>), zgrid, zblk, 0, st, in, wp, bias, s, xtiles, out, stats_partial, in_norm);
+        if (nt == 2) hipLaunchKernelGGL((ct_fwd_zslide_kernel<16, 2, 4, TO>), zgrid, zblk, 0, st, in, wp, bias, s, xtiles, out, stats_partial, in_norm);
         else hipLaunchKernelGGL((ct_fwd_zslide_kernel<16, 1, 4, TO>), zgrid, zblk, 0, st, in, wp, bias, s, xtiles, out, stats_partial, in_norm);
         S2D_LAUNCH_CHECK();
         return S2D_OK;
@@ -1609,10 +1600,8 @@ static int ct_fwd_launch(const TXI *in, const void *packed, const float *bias, i
     const dim3 grid(xcd_grid(blocks)), blk(256);
     // 3 z planes x (yc * yr + 2) input rows live per chunk of yc row groups
     const CtTileMap map = ct_tile_map(d, hg, xtiles, ct_chunk_rows((int64_t)w * cin * 4, yr, 2, 3));
-    if (cin == 32 && nt == 2) hipLaunchKernelGGL((ct_fwd_mfma_kernel<32, 2, 1, TO>), grid, blk, 0, st, in, wp, bias, s, xtiles, map, out, stats_partial, in_norm);
-    else if (cin == 32) hipLaunchKernelGGL((ct_fwd_mfma_kernel<32, 1, 1, TO>), grid, blk, 0, st, in, wp, bias, s, xtiles, map, out, stats_partial, in_norm);
-    else if (nt == 2) hipLaunchKernelGGL((ct_fwd_mfma_kernel<16, 2, 4, TO>), grid, blk, 0, st, in, wp, bias, s, xtiles, map, out, stats_partial, in_norm);
-    else hipLaunchKernelGGL((ct_fwd_mfma_kernel<16, 1, 4, TO>), grid, blk, 0, st, in, wp, bias, s, xtiles, map, out, stats_partial, in_norm);
+    if (nt == 2) hipLaunchKernelGGL((ct_fwd_mfma_kernel<32, 2, 1, TO>), grid, blk, 0, st, in, wp, bias, s, xtiles, map, out, stats_partial, in_norm);
+    else hipLaunchKernelGGL((ct_fwd_mfma_kernel<32, 1, 1, TO>), grid, blk, 0, st, in, wp, bias, s, xtiles, map, out, stats_partial, in_norm);
     S2D_LAUNCH_CHECK();
     return S2D_OK;
     }
@@ -1639,12 +1628,12 @@ extern "C" int s2d_convt3d_mfma_fwd_stats_y16_norm(const float *in, const float 
 }
 
 /* r06: ... reading a bf16-STORED raw input (the 16-channel z written in bf16 by s2d_pcr_level_fwd_y16_z16); stats tiles as for the fp32 input
- * with the z-sliding plan (s2d_convt3d_mfma_stats_tiles counts that plan when S2D_CT_ZSLIDE is on - the x16 path requires it) */
+ * with the z-sliding plan (the plan of every 16-channel input: s2d_convt3d_mfma_stats_tiles) */
 extern "C" int s2d_convt3d_mfma_fwd_stats_y16_norm_x16(const void *in_bf16, const float *in_scale_shift, const void *packed, const float *bias,
                                                        int batch, int cin, int cout, int d, int h, int w, void *out_bf16, float *stats_partial,
                                                        s2d_stream_t stream) {
     S2D_CHECK_ARG(in_scale_shift, "convt3d_mfma_fwd_stats_y16_norm_x16: null scale / shift");
-    if (!s2d_convt3d_mfma_x16_supported(cin, cout, d, h, w)) return S2D_ERR_UNSUPPORTED;   // includes the z-sliding plan (S2D_CT_ZSLIDE != 0)
+    if (!s2d_convt3d_mfma_x16_supported(cin, cout, d, h, w)) return S2D_ERR_UNSUPPORTED;
     return ct_fwd_launch<__bf16, __bf16>((const __bf16 *)in_bf16, packed, bias, batch, cin, cout, d, h, w, (__bf16 *)out_bf16, stats_partial, stream,
                                          in_scale_shift);
 }
@@ -1784,7 +1773,7 @@ extern "C" int s2d_convt3d_mfma_dgrad_d16(const void *dout_bf16, const void *pac
 }
 /* r06: ... writing the input gradient in bf16 as well (x16: the layer's input is the bf16-stored z, see s2d_convt3d_mfma_x16_supported) */
 extern "C" int s2d_convt3d_mfma_x16_supported(int cin, int cout, int d, int h, int w) {
-    return s2d_convt3d_mfma_norm_supported(cin, cout, d, h, w) && cin == 16 && cout <= 4 && w % 8 == 0 && ct_fwd_zslide(cin);
+    return s2d_convt3d_mfma_norm_supported(cin, cout, d, h, w) && cin == 16 && cout <= 4 && w % 8 == 0;
 }
 extern "C" int s2d_convt3d_mfma_dgrad_d16_x16(const void *dout_bf16, const void *packed, int batch, int cin, int cout, int d, int h, int w,
                                               void *din_bf16, s2d_stream_t stream) {

@@ -23,9 +23,10 @@
 //     step s -> ds_write in step s+1 -> read by every wave in step s+2; two LDS stages, one barrier per step.
 //   * no conditional memory operation and no peeled tail: the step count is padded to even with phantom steps (indices -1,
 //     clamped slab), so hipcc's vmcnt bookkeeping sees one straight loop body and keeps every load class in flight.
-//   * r03: the accumulators were updated by asm MFMAs ("+a") because the builtin made hipcc keep a second accumulator set and copy ~120
-//     registers per loop iteration.  End of r04: the asm form is wrong in one instantiation (RG_ASM_MFMA below) and the builtin is no
-//     longer slower; scheduling barriers pin the ds_read / memory / MFMA interleave either way.
+//   * the accumulators are updated by the compiler's MFMA builtin.  r03 wrote the MFMAs as inline asm with the accumulator tied in place
+//     ("+a") because the builtin then made hipcc keep a second accumulator set and copy ~120 registers per loop iteration; the asm form
+//     computed wrong rows in one instantiation (DESIGN rule 31: an asm statement is opaque to hipcc's hazard recognizer) and left the tree
+//     once the builtin was no slower.  Scheduling barriers pin the ds_read / memory / MFMA interleave.
 // The epilogue: bias, one bf16 rounding, 2*NJ-byte row stores, optional per-workgroup (sum, sum of squares) rows for the
 // BatchNorm1d that follows.
 #include "s2d_common.h"
@@ -39,15 +40,6 @@ typedef float f32x4r __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8r __attribute__((ext_vector_type(8)));
 
 constexpr int RG_KSTEP = 128;   // K elements per step
-#ifndef RG_ASM_MFMA
-// 0 (default since the end of r04): the compiler's MFMA builtin.  1: the r03 inline-asm MFMAs with the accumulator tied in place ("+a").  The asm form is WRONG
-// in the <128, 128, MI = 2, WAVES = 8> instantiation: the second tile of every wave comes out wrong above 32 768 output rows (DESIGN rule 31) - an inline asm
-// statement is opaque to hipcc's hazard recognizer, which therefore cannot keep a later write of an operand register (fragment reads, in-place refills) away from
-// an MFMA that is still reading it; the instantiation with the highest register pressure is where it bites.  With the builtin every instantiation is right at
-// the benchmark's row counts and no slower (ROCm 7.2's hipcc no longer copies the accumulator set per iteration, the reason r03 went to asm): 128 -> 128 at
-// 47 890 rows 43.9 us (asm: 45.7 us and wrong), 64 -> 128 26.1 (28.0), 128 -> 64 61.8 (63.6).
-#define RG_ASM_MFMA 0
-#endif
 #ifndef RG_BBURST
 #define RG_BBURST 1   // 1: all weight-slab pieces of a step are stored / re-requested in its first group (all 32 KiB in flight at once)
 #endif
@@ -375,14 +367,8 @@ __device__ __forceinline__ void rg_wave(const __bf16 *__restrict__ in, unsigned 
                     if (SORTED && !live[i][g / GPC]) continue;   // wave-uniform: this tile has no neighbour at the chunk's offset
 #pragma unroll
                     for (int n = 0; n < FG; ++n)
-                        // in-place accumulate in the AGPR file, written as asm: with the builtin hipcc gave the MFMAs a second
-                        // accumulator set (dst != src C) and copied ~120 registers back per loop iteration
-#if RG_ASM_MFMA
-                        asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][(g % GPC) * FG + n]) : "v"(a[i][g / GPC]), "v"(b[g & 1][n]));
-#else
                         acc[i][(g % GPC) * FG + n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8r, a[i][g / GPC]), __builtin_bit_cast(bf16x8r, b[g & 1][n]),
                                                                                                acc[i][(g % GPC) * FG + n], 0, 0, 0);
-#endif
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -398,7 +384,7 @@ __device__ __forceinline__ void rg_wave(const __bf16 *__restrict__ in, unsigned 
         step(s + 1, std::integral_constant<int, 1>{}, a1, idx1, kc1, kn1);
     }
 
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the accumulators were written by asm MFMAs: no hazard bookkeeping by the compiler
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // from the r03 asm-MFMA form (no hazard bookkeeping by the compiler there); kept: the instruction stream stays as measured
     // epilogue: C/D layout row = 4 q + reg, column (of tile n) = r  ->  output column r * NJ + n
     float bv[C::NJ], s1[C::NJ], s2[C::NJ];
 #pragma unroll

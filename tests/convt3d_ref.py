@@ -59,8 +59,6 @@ SHAPES = [
 ]
 SHAPE = {k: (cin, cout, shp) for k, cin, cout, shp in SHAPES}
 UNROUNDED = ["s03_co3", "s08", "s12a"]          # narrow, row-major and MFMA weight-gradient kernels; N4, COP 32 data gradients
-# shapes 2, 3, 4, 7 and 13, and 16 -> 17: the only road to the per-z kernel with two column tiles on 16 channels (S2D_CT_ZSLIDE=0)
-ZSLIDE_CHILD = ["s02", "s03_co1", "s03_co2", "s03_co3", "s03_co4", "s04", "s07a", "s07b", "s11d", "s13"]
 
 
 # ---- what the dispatch is expected to do (a host restatement of the launchers' predicates and of ct_wgrad_blocks_for) ------------------
@@ -81,8 +79,8 @@ def expect_norm(cin, cout, shp):
     return expect_d16(cin, cout, shp) and expect_narrow(cout, shp[3])
 
 
-def expect_x16(cin, cout, shp, zslide=1):
-    return expect_norm(cin, cout, shp) and cin == 16 and bool(zslide)
+def expect_x16(cin, cout, shp):
+    return expect_norm(cin, cout, shp) and cin == 16
 
 
 def wgrad_plan(cin, cout, shp):

@@ -1,10 +1,6 @@
 """TEST INFRASTRUCTURE ONLY - calls the twelve s2d_convt3d_mfma_* entries through the C ABI into caller-owned, poisoned, guarded buffers
-(tests/ws_guard.py) and measures them against tests/convt3d_ref.py.  Used by tests/test_convt3d_variants_gpu.py in process, and as a
-program by its S2D_CT_ZSLIDE cases: the library reads that variable once, so each value runs in a fresh child
-
-    python tests/convt3d_run.py zslide-child        (S2D_CT_ZSLIDE in the environment; prints one JSON line `CT_JSON {...}`)
+(tests/ws_guard.py) and measures them against tests/convt3d_ref.py.  Used by tests/test_convt3d_variants_gpu.py in process.
 """
-import json
 import os
 import sys
 
@@ -119,19 +115,17 @@ def _finish(rep, log):
 
 
 # ---- forward ----------------------------------------------------------------------------------------------------------------------------
-def forward_case(dc, rep, entries=FWD, x16_must_refuse=False):
+def forward_case(dc, rep):
     """every forward entry on one shape: float64 bars, the epilogue statistics and the bit identities; refusals where the predicate says no"""
     lib, c = _lib(), dc.c
     log = ws_guard.GuardLog(POISON)
-    ok = {e: predicate(lib, e, dc.cin, dc.cout, dc.shape) for e in entries}
+    ok = {e: predicate(lib, e, dc.cin, dc.cout, dc.shape) for e in FWD}
     got = {}
-    for e in entries:
+    for e in FWD:
         if not c["rounded"] and "_norm" in e:
             continue   # the unrounded inputs are for the forms without the fold
         x = dc.x16 if e.endswith("_x16") else dc.x
         rc, out, stats = call_fwd(lib, log, dc, e, x)
-        if e.endswith("_x16") and x16_must_refuse:
-            rep.add(f"{e} predicate off", "rc", ok[e], 0, not ok[e])
         if not ok[e]:
             _refused(rep, e, rc, [out, stats], POISON)
             continue
@@ -237,25 +231,3 @@ def wgrad_case(dc, rep):
     if "wgrad_d16_norm_x16" in a:
         rep.same("wgrad_d16_norm_x16 == wgrad_d16_norm", a["wgrad_d16_norm_x16"], a["wgrad_d16_norm"])
     return a
-
-
-# ---- the child of the S2D_CT_ZSLIDE cases ---------------------------------------------------------------------------------------------
-def zslide_child():
-    plan = int(os.environ["S2D_CT_ZSLIDE"])
-    result = {"plan": plan, "cases": {}}
-    for key in R.ZSLIDE_CHILD:
-        rep = R.Report()
-        dc = DeviceCase(R.case(key))
-        n, d, h, w = dc.shape
-        yr = 1 if dc.cin == 32 else 4
-        sliding = plan != 0 and (dc.cin == 16 or plan == 2)
-        want_tiles = n * (1 if sliding else d) * (-(-h // yr)) * (-(-w // 64))
-        rep.add("stats tiles of the plan", "rc", dc.tiles, want_tiles, dc.tiles == want_tiles)
-        forward_case(dc, rep, entries=("fwd_stats", "fwd_stats_y16", "fwd_stats_y16_norm", "fwd_stats_y16_norm_x16"), x16_must_refuse=plan == 0)
-        result["cases"][key] = rep.items
-    print("CT_JSON " + json.dumps(result), flush=True)
-
-
-if __name__ == "__main__":
-    assert sys.argv[1:] == ["zslide-child"], sys.argv
-    zslide_child()

@@ -165,7 +165,6 @@ def test_shapes_reach_the_predicates():
     assert e("s10") == (True, False, False)                           # cout <= 4 but not narrow: the fold is refused
     assert e("s08") == e("s09") == e("s11a") == e("s11b") == e("s11c") == e("s11d") == e("s13") == (True, False, False)
     assert e("s12a") == e("s12b") == (False, False, False)            # w % 4 != 0: every _d16 / _norm / _x16 entry refuses
-    assert not R.expect_x16(*R.SHAPE["s02"], zslide=0)
 
 
 def test_shapes_reach_the_tile_map_and_sweep_branches():

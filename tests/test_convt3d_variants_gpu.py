@@ -17,15 +17,9 @@ Per shape and group (forward / data gradient / weight gradient):
   * weight gradients run under both scratch poisons and give equal bits.
 Three shapes run again with unrounded fp32 x, w and dout (the forms without the fold): the reference rounds with torch, and the fp32-dout
 form must equal the _d16 form fed torch's rounding bit for bit - the loads round to nearest even.
-The S2D_CT_ZSLIDE = 0 / 2 forward plans run in one child process each (the library reads the variable once per process).
 
 Not reached: the staged data-gradient kernel (ct_dgrad_mfma_kernel) runs only when one sample's fp32 dout reaches 2 GB.
 """
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
@@ -33,7 +27,6 @@ import convt3d_ref as R
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 GROUPS = ("forward", "dgrad", "wgrad")
 _DC = {}
 
@@ -80,33 +73,3 @@ def test_unrounded_inputs_are_rounded_to_nearest_even_on_load(key, group):
     rep = R.Report()
     _run_group(group, _device_case(key, rounded=False), rep)
     rep.assert_all(f"{key} {group} unrounded")
-
-
-@pytest.mark.parametrize("plan", [0, 2])
-def test_zslide_plan_in_a_fresh_process(plan):
-    """S2D_CT_ZSLIDE=0: the per-z forward for 16 channels (and the _x16 forward refuses); =2: the z-sliding forward for 32 channels.  The
-    fp32-x forward entries over shapes 2, 3, 4, 7 and 13 (and 16 -> 17 of shape 11: with =0 the per-z kernel with two column tiles); the child
-    measures and prints, this test asserts."""
-    _DC.clear()
-    flags = [f for f, on in (("-s", sys.flags.no_user_site), ("-E", sys.flags.ignore_environment), ("-I", sys.flags.isolated)) if on]
-    env = dict(os.environ, S2D_CT_ZSLIDE=str(plan))
-    p = subprocess.run([sys.executable, *flags, os.path.join(HERE, "convt3d_run.py"), "zslide-child"], env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
-    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("CT_JSON ")]
-    assert len(lines) == 1, p.stdout[-2000:]
-    result = json.loads(lines[0][len("CT_JSON "):])
-    assert result["plan"] == plan and list(result["cases"]) == R.ZSLIDE_CHILD
-    reports = {key: R.Report(items) for key, items in result["cases"].items()}
-    for key, rep in reports.items():
-        whats = {i["what"] for i in rep.items}
-        cin, cout, shp = R.SHAPE[key]
-        assert {"fwd_stats y", "fwd_stats_y16 y", "y16 == bf16(y32)", "guards", "stats tiles of the plan"} <= whats, (key, sorted(whats))
-        if R.expect_norm(cin, cout, shp):
-            assert "y16_norm(x) == y16(relu(x * scale + shift))" in whats, (key, sorted(whats))
-        if plan == 0 and cin == 16:
-            assert {"fwd_stats_y16_norm_x16 predicate off", "fwd_stats_y16_norm_x16 refuses", "fwd_stats_y16_norm_x16 outputs untouched"} <= whats, key
-        if plan == 2 and R.expect_x16(cin, cout, shp):
-            assert "y16_norm_x16 == y16_norm" in whats, key
-    for key, rep in reports.items():
-        rep.assert_all(f"S2D_CT_ZSLIDE={plan} {key}")
