@@ -1381,6 +1381,43 @@ int s2d_track_step(const float *boxes, const int64_t *labels, const float *score
                    const double *ct_old, const double *tracking_old, const int32_t *meta_old, const int32_t *head_old, double *ct_new,
                    double *tracking_new, int32_t *meta_new, int32_t *head_new, int32_t *tracking_id, int32_t *active, s2d_stream_t stream);
 
+/* ---- detection AP evaluation (csrc/eval_ap.hip): the reference's KITTI-protocol evaluator (det3d/datasets/kitti/eval.py,
+ * det3d/datasets/utils/eval.py, rotate_iou_gpu_eval of det3d/ops/nms/nms_gpu.py), every frame of a split in ONE launch per entry.
+ *
+ * Rows of all frames are concatenated; det_off / gt_off DEVICE int32 [frames + 1] are the frames' row offsets and ov_off DEVICE int64
+ * [frames + 1] the offsets of their overlaps, ov_off[f + 1] - ov_off[f] = nd_f * ng_f.  A frame's overlaps are fp32 [ng_f][nd_f] (ground
+ * truth major).  At most S2D_EVAL_MAX_ROWS detections and as many ground-truth rows (DontCare included) per frame; the caller checks that.
+ * det_box / gt_box double [rows][7] = location, dimensions, rotation; det_img / gt_img double [rows][4] image boxes; det_score double
+ * [rows]; gt_occ_trunc double [rows][2] = occluded, truncated; det_name / gt_name int32 [rows]: the index of the lower-cased name in the
+ * reference's class table (0 car .. 10 cyclist), 11 van, 12 person_sitting, 15 anything else, plus 256 for the exact names DontCare / ignore.
+ *
+ * s2d_eval_overlaps: metric 0 image-box IoU (computed in double), 1 BEV IoU (fp32, the plane without z_axis), 2 3-D IoU (fp32 BEV
+ * intersection, the height term from z_axis / z_center in double), all rounded to fp32.
+ * classes / difficulties: HOST arrays (class 0..10, difficulty 0..2); min_overlaps DEVICE double [num_classes][num_overlaps], >= 0; a work
+ * item ("combination") is c = (class index * num_difficulties + difficulty index) * num_overlaps + overlap index.
+ * s2d_eval_match: the first pass (compute_fp=False).  tp_scores double [combinations][total_gt]: the scores of a frame's true positives in
+ * ground-truth order from [c][gt_off[f]]; counts int32 [frames][combinations][2] = true positives, ground truths that count; pr (the
+ * buffer of s2d_eval_pr) is cleared.
+ * s2d_eval_pr: the second pass (compute_fp=True) at thresholds DEVICE double [combinations][S2D_EVAL_SAMPLE_PTS], the first
+ * num_thresholds[c] of each; pr int64 [combinations][S2D_EVAL_SAMPLE_PTS][3] += tp, fp (after the DontCare subtraction of metric 0), fn
+ * over the frames: integer sums, the same bits on every call. */
+#define S2D_EVAL_MAX_ROWS 1024
+#define S2D_EVAL_MAX_CLASSES 11
+#define S2D_EVAL_SAMPLE_PTS 41
+int s2d_eval_overlaps(int metric, const double *det_box, const double *det_img, const double *gt_box, const double *gt_img,
+                      const int32_t *det_off, const int32_t *gt_off, const int64_t *ov_off, int frames, int64_t pairs, int z_axis,
+                      double z_center, float *overlaps, s2d_stream_t stream);
+int s2d_eval_match(const float *overlaps, const double *det_img, const double *det_score, const int32_t *det_name, const double *gt_img,
+                   const double *gt_occ_trunc, const int32_t *gt_name, const int32_t *det_off, const int32_t *gt_off, const int64_t *ov_off,
+                   int frames, const int32_t *classes, int num_classes, const int32_t *difficulties, int num_difficulties,
+                   const double *min_overlaps, int num_overlaps, int64_t total_gt, double *tp_scores, int32_t *counts, int64_t *pr,
+                   s2d_stream_t stream);
+int s2d_eval_pr(const float *overlaps, const double *det_img, const double *det_score, const int32_t *det_name, const double *gt_img,
+                const double *gt_occ_trunc, const int32_t *gt_name, const int32_t *det_off, const int32_t *gt_off, const int64_t *ov_off,
+                int frames, int metric, const int32_t *classes, int num_classes, const int32_t *difficulties, int num_difficulties,
+                const double *min_overlaps, int num_overlaps, const double *thresholds, const int32_t *num_thresholds, int64_t *pr,
+                s2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

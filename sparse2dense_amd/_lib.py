@@ -493,6 +493,15 @@ SIGNATURES = {
     # center-based tracker: every segment's step in one launch (csrc/tracking.hip)
     "s2d_track_step": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_float] + [ctypes.c_void_p] * 10 + [ctypes.c_void_p]),
+    # detection AP evaluation: overlaps, first-pass matching and the threshold sweep, one launch each for a whole split (csrc/eval_ap.hip)
+    "s2d_eval_overlaps": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_eval_match": (ctypes.c_int, [ctypes.c_void_p] * 10 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]
+                       + [ctypes.c_void_p] * 3 + [ctypes.c_void_p]),
+    "s2d_eval_pr": (ctypes.c_int, [ctypes.c_void_p] * 10 + [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                   ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                    + [ctypes.c_void_p] * 3 + [ctypes.c_void_p]),
 }
 
 _lib = None

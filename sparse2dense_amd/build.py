@@ -34,7 +34,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # prep.hip: the inside test and the rotations are pairs of fp32 products and sums, packed-FP32 candidates, and the frame of step k + 1 is
 # prepared on the prefetch stream beside step k's MFMA kernels (rule 36).
 # tracking.hip: its decisions rest on fp32 products and sums rounded one by one, and the online tracker runs behind predict (rule 36).
-EXTRA = {"deform_conv.hip": ["-fno-slp-vectorize"], "center_predict.hip": ["-fno-slp-vectorize"], "roi_head.hip": ["-fno-slp-vectorize"],
+# eval_ap.hip: every overlap decision rests on fp32 products and sums of the rectangle intersection rounded one by one, as nms.hip's.
+EXTRA = {"eval_ap.hip": ["-fno-slp-vectorize"], "deform_conv.hip": ["-fno-slp-vectorize"], "center_predict.hip": ["-fno-slp-vectorize"], "roi_head.hip": ["-fno-slp-vectorize"],
          "anchor_predict.hip": ["-fno-slp-vectorize"], "roi_mlp.hip": ["-fno-slp-vectorize"], "pillar_distill.hip": ["-fno-slp-vectorize"],
          "prep.hip": ["-fno-slp-vectorize"], "tracking.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("S2D_BUILD_LOSSES_SLP") != "1":

@@ -180,6 +180,16 @@ def install():
     _module("det3d.datasets")
     _module("det3d.datasets.pipelines")
     _module("det3d.datasets.pipelines.preprocess", Preprocess=prep.S2DPreprocess)
+    from . import evaluation as ev
+    _module("det3d.datasets.kitti")
+    _module("det3d.datasets.kitti.eval", **{k: getattr(ev, k) for k in [
+        "get_thresholds", "clean_data", "eval_class_v3", "get_mAP", "do_eval_v3", "do_coco_style_eval", "get_official_eval_result",
+        "get_coco_eval_result"]})
+    _module("det3d.datasets.utils")
+    _module("det3d.datasets.utils.eval", **{k: getattr(ev, k) for k in [
+        "calculate_iou_partly", "compute_statistics_jit", "prepare_data", "bev_box_overlap", "box3d_overlap", "image_box_overlap"]})
+    _module("det3d.ops.nms")
+    _module("det3d.ops.nms.nms_gpu", rotate_iou_gpu_eval=ev.rotate_iou_gpu_eval)
     if "spconv" not in sys.modules:
         _module("spconv", SparseConvTensor=spconv.SparseConvTensor, SubMConv3d=spconv.SubMConv3d,
                 SparseConv3d=spconv.SparseConv3d, SparseSequential=spconv.SparseSequential,
