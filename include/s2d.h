@@ -885,6 +885,32 @@ int s2d_nms_circle_batched(const float *xy, int xy_stride, const int32_t *offset
                            s2d_stream_t stream);
 
 /*
+ * The two kernels that let CenterHead.predict run without the host (center_predict.StaticPredictPlan): a selection in place of the full
+ * sort of the score rows, and an assembly into outputs of fixed capacity.
+ *
+ * s2d_segment_topk (csrc/segment_topk.hip), one workgroup per row, no communication between workgroups: for every row s of score
+ * [segments][row_stride] (row_len <= row_stride, row_len <= 2^20, 1 <= k <= 4096) ranks r < min(k, row_len) of the row's STABLE
+ * DESCENDING sort go to order[s * out_stride + r] (int64 index into the row) and score_sorted[s * out_stride + r] (the element, bit for
+ * bit); entries at r >= min(k, row_len) are not touched.  Comparison is by float value: -0.0 == +0.0, -inf is the lowest value, equal
+ * values go in ascending index order - the first k columns of torch.sort(row, descending=True, stable=True).  NaN is outside the
+ * contract (the score kernel never writes it); it costs no out-of-bounds access.  With passed (DEVICE int32 [segments], the pass counts
+ * s2d_center_predict_score wrote) the entry also writes the segment table of the packed lists of k rows per segment that
+ * s2d_center_predict_boxes and the batched NMS read: offsets[s] = s * k, counts[s] = min(passed[s], k), overflow[s] = passed[s] > k
+ * (all DEVICE int32 [segments]); passed == NULL: no table.
+ *
+ * s2d_predict_static_gather (csrc/center_predict.hip), one workgroup per sample: walks the sample's tasks in task order and copies the
+ * first min(n_keep[s], max_keep) kept rows keep[s][i] (indices into the segment's own rows, from row offsets[s] of the packed lists of
+ * `total` rows) of each segment s = task * samples + sample into boxes [samples][cap][box_dim], scores [samples][cap], labels
+ * [samples][cap] (int64), cap = tasks * max_keep, and their number into counts [samples] (int32).  Rows at or past counts[b] are written
+ * too: boxes and scores zero, label -1.
+ */
+int s2d_segment_topk(const float *score, int segments, int64_t row_len, int64_t row_stride, int k, const int32_t *passed, int64_t *order,
+                     float *score_sorted, int64_t out_stride, int32_t *offsets, int32_t *counts, int32_t *overflow, s2d_stream_t stream);
+int s2d_predict_static_gather(const float *cand_boxes, const float *cand_scores, const int64_t *cand_labels, const int32_t *offsets,
+                              const int64_t *keep, const int32_t *n_keep, int tasks, int samples, int max_keep, int box_dim, int64_t total,
+                              float *boxes, float *scores, int64_t *labels, int32_t *counts, s2d_stream_t stream);
+
+/*
  * CenterPoint training targets on the device = AssignLabel.__call__ (det3d/datasets/pipelines/preprocess.py:489-653, one-task
  * Waymo head) with gaussian_radius / draw_umich_gaussian (det3d/core/utils/center_utils.py:18-64).  gt_boxes fp32
  * [frames][max_boxes][9] (x,y,z,w,l,h,vx,vy,yaw), gt_classes int32 [frames][max_boxes] (1-based, <= 0 = padding).  Outputs per

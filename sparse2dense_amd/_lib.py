@@ -280,6 +280,9 @@ SIGNATURES = {
                                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "s2d_nms_circle_batched": (ctypes.c_int, [c_f32p, ctypes.c_int, c_i32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_f32p,
                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "s2d_segment_topk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    "s2d_predict_static_gather": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_int64] + [ctypes.c_void_p] * 5),
     "s2d_assign_label": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_float * 2, ctypes.c_float * 2] + [ctypes.c_int] * 5 +
                          [ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 7),
     "s2d_assign_label_tasks": (ctypes.c_int, [c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,

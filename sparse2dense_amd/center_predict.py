@@ -1,7 +1,9 @@
 """CenterHead.predict on the device (csrc/center_predict.hip): the decode of every task and sample of a head in two launches around one
 sort, and the assembly of the per-sample results from the batched NMS (nms.rotate_nms_batched / nms.circle_nms_batched).
 Replaces the per-task torch chain of /root/reference/det3d/models/bbox_heads/center_head.py:311-419 and the per-(task, sample) chain
-of :452-495.  A SEGMENT is one (task, sample) pair, segment = task * samples + sample."""
+of :452-495.  A SEGMENT is one (task, sample) pair, segment = task * samples + sample.
+`StaticPredictPlan` (below) is the same predict without the host: a device top-K select (csrc/segment_topk.hip) in place of the sort,
+fixed-capacity buffers allocated once, launches only - the form a HIP graph can hold."""
 import ctypes
 from collections import namedtuple
 
@@ -159,3 +161,174 @@ def predict_on_device(preds_dicts, test_cfg, num_classes):
     else:
         boxes, scores, labels = cand.boxes[:0], cand.scores[:0], cand.labels[:0]
     return list(zip(boxes.split(sizes), scores.split(sizes), labels.split(sizes)))
+
+
+# ---- predict without the host: fixed-capacity buffers, launches only, capturable into one HIP graph --------------------------------------
+TOPK_MAX = 4096   # s2d_segment_topk's limit on k
+
+
+class StaticDetections:
+    """Padded results of `StaticPredictPlan.run`, all on the device and owned by the plan (the next run overwrites them):
+    boxes [B, cap, 7 | 9] fp32, scores [B, cap] fp32, labels [B, cap] int64 - the first counts[b] (int32 [B]) rows of sample b are its
+    detections in `predict`'s order, the rows behind them are zero with label -1; overflow int32 [tasks * B]: 1 where a (task, sample)
+    segment had more passing pixels than the plan's k (its result is then the NMS of its k best)."""
+    __slots__ = ("boxes", "scores", "labels", "counts", "overflow")
+
+    def __init__(self, boxes, scores, labels, counts, overflow):
+        self.boxes, self.scores, self.labels, self.counts, self.overflow = boxes, scores, labels, counts, overflow
+
+    def __iter__(self):
+        return iter((self.boxes, self.scores, self.labels, self.counts, self.overflow))
+
+    def as_list(self, metadata=None):
+        """what `CenterHead.predict` returns: one dict per sample (box3d_lidar, scores, label_preds, metadata), views into the padded
+        buffers.  The ONE host read of the static path: the counts."""
+        counts = self.counts.tolist()
+        return [dict(box3d_lidar=self.boxes[b, :n], scores=self.scores[b, :n], label_preds=self.labels[b, :n],
+                     metadata=metadata[b] if metadata else None) for b, n in enumerate(counts)]
+
+
+def _static_maps(preds_dicts):
+    """the refusals of the static path that concern the maps, before any HIP call: it reads the maps in place, so it cannot widen or copy"""
+    if not 1 <= len(preds_dicts) <= MAX_TASKS:
+        raise _lib.S2DError(f"predict_static: {len(preds_dicts)} tasks (1..{MAX_TASKS} supported)")
+    has_vel = "vel" in preds_dicts[0]
+    for preds in preds_dicts:
+        if ("vel" in preds) != has_vel:
+            raise _lib.S2DError("predict_static: a velocity branch on some tasks only")
+        for key in _MAPS:
+            if key == "vel" and not has_vel:
+                continue
+            t = preds[key]
+            if t.dtype != torch.float32:
+                raise _lib.S2DError(f"predict_static: map '{key}' is {t.dtype}: fp32 maps only (the static path does not widen)")
+            if t.dim() != 4 or not (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)):
+                raise _lib.S2DError(f"predict_static: map '{key}' is neither NCHW-contiguous nor channels_last (the static path does not copy)")
+    if not all(v.is_cuda for p in preds_dicts for v in p.values()):
+        raise _lib.S2DError("predict_static: CUDA tensors expected (no CPU fallback)")
+    return has_vel
+
+
+class StaticPredictPlan:
+    """CenterHead.predict for one (test_cfg, class counts, samples, h, w, velocity branch, device) with every buffer allocated at build
+    time.  `run` only launches on the current stream - score, top-K, boxes, batched NMS, gather: seven kernels - with no host read, no
+    host-to-device copy, no allocation and no torch operator, so it can be captured into a HIP graph (one stream, a linear chain).
+    k candidates per segment: nms_pre_max_size under the rotated NMS (the cut `predict` makes: equal results whatever passes);
+    `max_candidates` under the circle NMS, where `predict` takes every passing pixel - a segment with more gets overflow = 1 and the NMS of
+    its k best."""
+
+    def __init__(self, test_cfg, num_classes, samples, h, w, has_vel, device, max_candidates=4096):
+        get = _cfg_get(test_cfg)
+        nms_cfg = get("nms")
+        nget = (lambda k: nms_cfg[k]) if isinstance(nms_cfg, dict) else (lambda k: getattr(nms_cfg, k))
+        device = torch.device(device)
+        self.circular = bool(get("circular_nms", False))
+        self.double_flip = bool(get("double_flip", False))
+        self.tasks, self.samples, self.h, self.w = len(num_classes), int(samples), int(h), int(w)
+        self.k = int(max_candidates if self.circular else nget("nms_pre_max_size"))
+        if not 1 <= self.k <= TOPK_MAX:
+            raise _lib.S2DError(f"StaticPredictPlan: {self.k} candidates per segment (1..{TOPK_MAX} supported)")
+        if not 1 <= self.tasks <= MAX_TASKS:
+            raise _lib.S2DError(f"StaticPredictPlan: {self.tasks} tasks (1..{MAX_TASKS} supported)")
+        if device.type != "cuda":
+            raise _lib.S2DError("StaticPredictPlan: a CUDA device expected (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.samples < 1 or self.h < 1 or self.w < 1:
+            raise _lib.S2DError(f"StaticPredictPlan: empty maps (samples {samples}, h {h}, w {w})")
+        if get("per_class_nms", False):
+            raise NotImplementedError("StaticPredictPlan: per_class_nms produces no result in the reference either (center_head.py:417-418)")
+        if self.circular and len(get("min_radius")) < self.tasks:
+            raise _lib.S2DError(f"StaticPredictPlan: {len(get('min_radius'))} circle radii for {self.tasks} tasks")
+        lib = _lib.load()
+        from .nms import _ws
+        self.device, self.has_vel = device, bool(has_vel)
+        self.classes = [int(c) for c in num_classes]
+        self.label_bases = [sum(self.classes[:t]) for t in range(self.tasks)]
+        rng = get("post_center_limit_range")
+        self.range6 = (ctypes.c_float * 6)(*[float(v) for v in rng]) if rng is not None and len(rng) > 0 else None
+        vs, pc0 = get("voxel_size"), get("pc_range")
+        self.geo = (float(get("out_size_factor")), float(vs[0]), float(vs[1]), float(pc0[0]), float(pc0[1]))
+        self.threshold = float(get("score_threshold"))
+        self.iou_threshold = float(nget("nms_iou_threshold"))
+        post_max = nget("nms_post_max_size")
+        self.max_keep = self.k if post_max is None else min(self.k, int(post_max))
+        segs, hw, k, nd = self.tasks * self.samples, self.h * self.w, self.k, 9 if has_vel else 7
+        self.segs, self.hw, self.box_dim, self.total, self.cap = segs, hw, nd, segs * k, self.tasks * self.max_keep
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+        self.score, self.label, self.passed = new((segs, hw), torch.float32), new((segs, hw), torch.int32), new((segs,), torch.int32)
+        # row stride h * w, the first k columns filled: s2d_center_predict_boxes reads them as it reads a full sort
+        self.order, self.score_sorted = new((segs, hw), torch.int64), new((segs, hw), torch.float32)
+        self.table = new((3, segs), torch.int32)   # offsets, counts, overflow
+        self.cand_boxes, self.cand_scores, self.cand_labels = new((self.total, nd), torch.float32), new((self.total,), torch.float32), new((self.total,), torch.int64)
+        self.keep, self.n_keep = new((segs, self.max_keep), torch.int64), new((segs,), torch.int32)
+        self.nms_ws = _ws(lib.s2d_nms_batched_workspace_bytes(self.total, k), device)
+        self.radius = None
+        if self.circular:
+            radius = [float(get("min_radius")[t]) for t in range(self.tasks) for _ in range(self.samples)]
+            self.radius = torch.tensor(radius, dtype=torch.float32).to(device)
+        self.boxes, self.scores = new((self.samples, self.cap, nd), torch.float32), new((self.samples, self.cap), torch.float32)
+        self.labels, self.counts = new((self.samples, self.cap), torch.int64), new((self.samples,), torch.int32)
+        self.out = StaticDetections(self.boxes, self.scores, self.labels, self.counts, self.table[2])
+
+    def buffers(self):
+        """every device buffer of the plan by name (none is ever reallocated)"""
+        names = ("score", "label", "passed", "order", "score_sorted", "table", "cand_boxes", "cand_scores", "cand_labels", "keep", "n_keep", "nms_ws",
+                 "radius", "boxes", "scores", "labels", "counts")
+        return {n: getattr(self, n) for n in names if getattr(self, n) is not None}
+
+    def _task_table(self, preds_dicts):
+        if _static_maps(preds_dicts) != self.has_vel or len(preds_dicts) != self.tasks:
+            raise _lib.S2DError("StaticPredictPlan.run: the tasks or the velocity branch differ from the plan's")
+        images = self.samples * (4 if self.double_flip else 1)
+        table = (_lib.CenterPredictTask * self.tasks)()
+        for rec, preds, classes, base in zip(table, preds_dicts, self.classes, self.label_bases):
+            for m, key in enumerate(_MAPS):
+                if key == "vel" and not self.has_vel:
+                    continue
+                t = preds[key]
+                c = classes if key == "hm" else _CHANNELS[key]
+                if tuple(t.shape) != (images, c, self.h, self.w) or t.device != self.device:
+                    raise _lib.S2DError(f"StaticPredictPlan.run: map '{key}' has shape {tuple(t.shape)} on {t.device}, the plan was built for "
+                                        f"{(images, c, self.h, self.w)} on {self.device}")
+                rec.map[m] = t.data_ptr()
+                rec.channel_stride[m], rec.pixel_stride[m] = (self.hw, 1) if t.is_contiguous() else (1, c)
+            rec.classes, rec.label_base = classes, base
+        return table
+
+    def run(self, preds_dicts):
+        """launches only, on the current stream; returns the plan's `StaticDetections` (the same tensors at every call)"""
+        table = self._task_table(preds_dicts)   # host only: pointers and strides of the maps, read in place
+        lib, st, flip, ptr = _lib.load(), _stream(self.device), int(self.double_flip), lambda t: t.data_ptr()
+        offsets, counts, overflow = (self.table[i].data_ptr() for i in range(3))
+        _lib.check(lib.s2d_center_predict_score(table, self.tasks, self.samples, self.h, self.w, flip, self.threshold, self.range6, *self.geo,
+                                                ptr(self.score), ptr(self.label), ptr(self.passed), st), "s2d_center_predict_score")
+        _lib.check(lib.s2d_segment_topk(ptr(self.score), self.segs, self.hw, self.hw, self.k, ptr(self.passed), ptr(self.order), ptr(self.score_sorted),
+                                        self.hw, offsets, counts, overflow, st), "s2d_segment_topk")
+        _lib.check(lib.s2d_center_predict_boxes(table, self.tasks, self.samples, self.h, self.w, flip, *self.geo, ptr(self.order), ptr(self.score_sorted),
+                                                ptr(self.label), offsets, counts, self.k, self.total, ptr(self.cand_boxes), ptr(self.cand_scores),
+                                                ptr(self.cand_labels), st), "s2d_center_predict_boxes")
+        if self.circular:
+            rc = lib.s2d_nms_circle_batched(ptr(self.cand_boxes), self.box_dim, offsets, counts, self.segs, self.k, self.total, ptr(self.radius),
+                                            self.max_keep, ptr(self.keep), ptr(self.n_keep), ptr(self.nms_ws), self.nms_ws.numel(), st)
+        else:
+            rc = lib.s2d_nms_rotated_bev_batched(ptr(self.cand_boxes), self.box_dim, offsets, counts, self.segs, self.k, self.total, self.iou_threshold,
+                                                 self.max_keep, ptr(self.keep), ptr(self.n_keep), ptr(self.nms_ws), self.nms_ws.numel(), st)
+        _lib.check(rc, "s2d_nms_circle_batched" if self.circular else "s2d_nms_rotated_bev_batched")
+        _lib.check(lib.s2d_predict_static_gather(ptr(self.cand_boxes), ptr(self.cand_scores), ptr(self.cand_labels), offsets, ptr(self.keep),
+                                                 ptr(self.n_keep), self.tasks, self.samples, self.max_keep, self.box_dim, self.total, ptr(self.boxes),
+                                                 ptr(self.scores), ptr(self.labels), ptr(self.counts), st), "s2d_predict_static_gather")
+        return self.out
+
+
+def static_plan_key(test_cfg, num_classes, images, h, w, has_vel, device, max_candidates):
+    """what a StaticPredictPlan depends on, as a hashable key (CenterHead.predict_static caches plans by it)"""
+    get = _cfg_get(test_cfg)
+    nms_cfg = get("nms")
+    nget = (lambda k: nms_cfg[k]) if isinstance(nms_cfg, dict) else (lambda k: getattr(nms_cfg, k))
+    flat = lambda v: None if v is None else tuple(float(x) for x in v)
+    circular = bool(get("circular_nms", False))
+    return (float(get("score_threshold")), flat(get("post_center_limit_range")), float(get("out_size_factor")), flat(get("voxel_size")),
+            flat(get("pc_range")), bool(get("double_flip", False)), circular, flat(get("min_radius")) if circular else None,
+            nget("nms_pre_max_size"), nget("nms_post_max_size"), float(nget("nms_iou_threshold")), bool(get("per_class_nms", False)),
+            tuple(num_classes), int(images), int(h), int(w), bool(has_vel), str(device), int(max_candidates))

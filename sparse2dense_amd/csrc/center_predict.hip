@@ -6,6 +6,8 @@
 //   center_boxes_kernel   decodes the full box of the n_s best pixels of every segment into one packed list
 //   nms_batched_*_kernel  suppression bit matrices of all segments in one launch (rotated IoU or centre distance: the pair tests of
 //                         nms.hip, unchanged), then the greedy walk with ONE WORKGROUP PER SEGMENT - the walks are independent
+//   predict_static_gather_kernel  (the static path, center_predict.StaticPredictPlan: s2d_segment_topk of segment_topk.hip in place of
+//                         the sort, no host read) the kept rows of every sample into outputs of fixed capacity, padding written
 // The per-task map pointers and strides travel by value in the kernel arguments (s2d_center_predict_task[8], as s2d_center_task[8] does
 // for the loss).  Expression order follows the torch chain (the library is built with -ffp-contract=off): the flip mean is the
 // left-to-right sum of the four views times 0.25, x = (col + reg_x) * out_size_factor * voxel_x + pc_x.
@@ -258,6 +260,43 @@ __global__ __launch_bounds__(256) void nms_batched_select_kernel(const int32_t *
     if (threadIdx.x == 0) n_keep[seg] = *count < max_keep ? *count : max_keep;
 }
 
+// ---- fixed-capacity assembly ----------------------------------------------------------------------------------------------------------
+// One workgroup per sample: the kept rows of its segments (task * samples + sample) in task order, as predict_on_device's gather lays
+// them out, into slots of tasks * max_keep rows; the rows behind the sample's count are written as well (zero boxes and scores, label
+// -1), so the outputs are defined everywhere.  A kept index outside the packed list (a wrong device array) gives such a padding row.
+__global__ __launch_bounds__(256) void predict_static_gather_kernel(const float *__restrict__ cand_boxes, const float *__restrict__ cand_scores,
+                                                                    const int64_t *__restrict__ cand_labels, const int32_t *__restrict__ offsets,
+                                                                    const int64_t *__restrict__ keep, const int32_t *__restrict__ n_keep, int tasks,
+                                                                    int samples, int max_keep, int box_dim, int64_t total, float *__restrict__ boxes,
+                                                                    float *__restrict__ scores, int64_t *__restrict__ labels,
+                                                                    int32_t *__restrict__ counts) {
+    const int b = blockIdx.x;
+    const int64_t cap = (int64_t)tasks * max_keep;
+    float *out_boxes = boxes + b * cap * box_dim, *out_scores = scores + b * cap;
+    int64_t *out_labels = labels + b * cap;
+    int64_t count = 0;
+    for (int t = 0; t < tasks; ++t) {
+        const int seg = t * samples + b;
+        const int n = min(max(n_keep[seg], 0), max_keep);
+        const int64_t off = offsets[seg];
+        for (int i = threadIdx.x; i < n; i += 256) {
+            int64_t row = off + keep[(int64_t)seg * max_keep + i];
+            if (row < 0 || row >= total || off < 0) row = -1;
+            float *dst = out_boxes + (count + i) * box_dim;
+            for (int c = 0; c < box_dim; ++c) dst[c] = row < 0 ? 0.f : cand_boxes[row * box_dim + c];
+            out_scores[count + i] = row < 0 ? 0.f : cand_scores[row];
+            out_labels[count + i] = row < 0 ? -1 : cand_labels[row];
+        }
+        count += n;
+    }
+    for (int64_t i = count + threadIdx.x; i < cap; i += 256) {
+        for (int c = 0; c < box_dim; ++c) out_boxes[i * box_dim + c] = 0.f;
+        out_scores[i] = 0.f;
+        out_labels[i] = -1;
+    }
+    if (threadIdx.x == 0) counts[b] = (int32_t)count;
+}
+
 static int check_tasks(const char *what, const s2d_center_predict_task *tasks, int num_tasks, int samples, int h, int w, PredictTasks &out) {
     S2D_CHECK_ARG(tasks, "%s: null task table", what);
     S2D_CHECK_ARG(num_tasks >= 1 && num_tasks <= CP_MAX_TASKS, "%s: %d tasks (1..%d supported)", what, num_tasks, CP_MAX_TASKS);
@@ -372,4 +411,20 @@ extern "C" int s2d_nms_circle_batched(const float *xy, int xy_stride, const int3
                                       s2d_stream_t stream) {
     return nms_batched<true>("nms_circle_batched", xy, xy_stride, offsets, counts, segments, max_count, total, thresh, 0.f, max_keep, keep, n_keep, ws,
                              ws_bytes, stream);
+}
+
+extern "C" int s2d_predict_static_gather(const float *cand_boxes, const float *cand_scores, const int64_t *cand_labels, const int32_t *offsets,
+                                         const int64_t *keep, const int32_t *n_keep, int tasks, int samples, int max_keep, int box_dim, int64_t total,
+                                         float *boxes, float *scores, int64_t *labels, int32_t *counts, s2d_stream_t stream) {
+    S2D_CHECK_ARG(tasks >= 1 && tasks <= CP_MAX_TASKS, "predict_static_gather: %d tasks (1..%d supported)", tasks, CP_MAX_TASKS);
+    S2D_CHECK_ARG(samples >= 0 && samples <= 65535 && max_keep >= 0 && total >= 0, "predict_static_gather: bad size (samples %d, max_keep %d, total %lld)",
+                  samples, max_keep, (long long)total);
+    S2D_CHECK_ARG(box_dim == 7 || box_dim == 9, "predict_static_gather: box_dim %d (7 or 9)", box_dim);
+    if (samples == 0) return S2D_OK;
+    S2D_CHECK_ARG(offsets && n_keep && counts, "predict_static_gather: null segment arrays or counts");
+    S2D_CHECK_ARG(max_keep == 0 || (cand_boxes && cand_scores && cand_labels && keep && boxes && scores && labels), "predict_static_gather: null argument");
+    hipLaunchKernelGGL(predict_static_gather_kernel, dim3((unsigned)samples), dim3(256), 0, (hipStream_t)stream, cand_boxes, cand_scores, cand_labels,
+                       offsets, keep, n_keep, tasks, samples, max_keep, box_dim, total, boxes, scores, labels, counts);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
 }

@@ -907,6 +907,8 @@ class CenterHead(nn.Module):
         self.use_direction_classifier = False
         self.logger = logger or logging.getLogger("CenterHead")
         self.predict_paths = {"device": 0, "torch": 0}   # calls of predict() by the path they took
+        self.static_predict_calls = 0   # calls of predict_static() (opt-in: predict() never takes it)
+        self._static_plans = {}
         self.shared_conv = nn.Sequential(*fuse_bn_relu([Conv3x3(in_channels, share_conv_channel, 3, padding=1, bias=True),
                                                         FastBatchNorm2d(share_conv_channel), nn.ReLU(inplace=True)]))
         self.tasks = nn.ModuleList()
@@ -1019,6 +1021,33 @@ class CenterHead(nn.Module):
         if meta and get("double_flip", False):
             meta = meta[:4 * len(per_sample):4]
         return [dict(box3d_lidar=b, scores=s, label_preds=l, metadata=meta[i] if meta else None) for i, (b, s, l) in enumerate(per_sample)]
+
+    @torch.no_grad()
+    def predict_static(self, example, preds_dicts, test_cfg, max_candidates=4096):
+        """`predict` without the host (center_predict.StaticPredictPlan: launches only, fixed-capacity outputs, capturable into a HIP
+        graph).  Opt-in; the plans are cached on the head, one per (test_cfg, map sizes, velocity branch, device, max_candidates).
+        Returns (StaticDetections, metadata): padded device tensors owned by the plan - the next call with the same plan overwrites
+        them - and the example's metadata per sample; `detections.as_list(metadata)` gives what `predict` returns, with one host read.
+        Refused with S2DError before any HIP call: more than 4096 candidates per segment or 8 tasks, CPU maps, maps that are not fp32
+        in NCHW or channels_last, a velocity branch on some tasks only.  static_predict_calls counts the calls."""
+        has_vel = center_predict._static_maps(preds_dicts)
+        hm0 = preds_dicts[0]["hm"]
+        images, _, h, w = hm0.shape
+        key = center_predict.static_plan_key(test_cfg, self.num_classes, images, h, w, has_vel, hm0.device, max_candidates)
+        plans = self._static_plans
+        plan = plans.get(key)
+        if plan is None:
+            flip = bool(center_predict._cfg_get(test_cfg)("double_flip", False))
+            if flip and images % 4:
+                raise center_predict._lib.S2DError(f"predict_static: {images} images under double_flip (four per sample expected)")
+            plan = plans[key] = center_predict.StaticPredictPlan(test_cfg, self.num_classes, images // 4 if flip else images, h, w, has_vel,
+                                                                 hm0.device, max_candidates)
+        out = plan.run(preds_dicts)
+        self.static_predict_calls += 1
+        meta = example.get("metadata") if isinstance(example, dict) else None
+        if meta and plan.double_flip:
+            meta = meta[:4 * plan.samples:4]
+        return out, meta
 
     @torch.no_grad()
     def predict_torch(self, example, preds_dicts, test_cfg, **kwargs):
