@@ -47,6 +47,7 @@ typedef void *s2d_stream_t;
 #define S2D_ERR_COMM (-5)
 
 /* ---- library ------------------------------------------------------------------------------ */
+/* 101: s2d_spconv_s16_sorted_supported / s2d_spconv_s16_fwd_sorted no longer take 64 -> 64 layers (128 -> 128 only); 100 before */
 int s2d_version(void);
 /* copies the calling thread's last error text (NUL terminated) into buf; returns its length */
 int s2d_last_error(char *buf, size_t buf_len);
@@ -455,11 +456,10 @@ int s2d_spconv_s16_fwd_stats(const void *in_feat, int64_t n_in, const void *pack
  * rows: every workgroup multiplies only the kernel offsets present in the union of its rows' masks, every wave only those present in its
  * 16-row tile; results are stored to the canonical rows perm[j], so out_feat (and stats_partial: the same
  * [s2d_spconv_s16_stats_tiles][2][cout] layout) are what s2d_spconv_s16_fwd_stats returns, up to the summation order of the statistics.
- * Supported: kvol 27, 64 -> 64 and 128 -> 128 channels (s2d_spconv_s16_sorted_supported).
+ * Supported: kvol 27, 128 -> 128 channels (s2d_spconv_s16_sorted_supported).
  * OPT-IN: measured on the benchmark scene's rulebooks (profiles/r06_sparse_sorted_rows_ab.txt) the sorted form is 5-10 % SLOWER than the
  * plain kernel although it issues 37 % fewer MFMAs - the kernel is bound by the gathered rows, which skipping does not reduce.
- * s2d_spconv_s16_set_sorted_rows(1) (or S2D_RG_SORTED=1 in the environment) switches it on and returns the previous setting; it also
- * moves 64 -> 64 layers to the register-gather weight image, so packed images made before the switch must be rebuilt.
+ * s2d_spconv_s16_set_sorted_rows(1) (or S2D_RG_SORTED=1 in the environment) switches it on and returns the previous setting.
  */
 int s2d_spconv_s16_set_sorted_rows(int on);
 size_t s2d_rulebook_sort_workspace_bytes(int64_t n);

@@ -547,8 +547,9 @@ def load():
         fn.argtypes = args
     # Pure shape queries (workspace sizes, launch plans, *_supported) are asked again with the same integers by every layer call of every step
     # - ~150 ctypes round trips of 3-5 us per training step on the launch thread.  They depend on their integer arguments and on
-    # environment switches the library reads once, so the answers are memoised per argument tuple.  (Not the queries that follow a
-    # run-time mode: the sparse bf16-storage kernels' plans change with the sorted-row switch.)
+    # environment switches the library reads once, so the answers are memoised per argument tuple.  (Not the sparse bf16-storage
+    # kernels' queries: they follow S2D_RG_PLAN / S2D_S16_PLAN, which the library reads again on every call, and *_sorted_supported
+    # the sorted-row switch.)
     _int_types = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t)
     for name, (res, args) in SIGNATURES.items():
         pure = name.endswith(("_workspace_bytes", "_supported", "_stats_tiles", "_tile_rows", "_packed_elems")) and "sort" not in name and "spconv_s16" not in name

@@ -68,7 +68,7 @@ extern "C" int s2d_debug_lds_fill(float value, int blocks, int spin, float *sink
     return S2D_OK;
 }
 
-extern "C" int s2d_version(void) { return 100; }
+extern "C" int s2d_version(void) { return 101; }
 
 /* compiler / runtime the library was built with (the MFMA builtin path of csrc/spconv_rg.hip ties its code quality to the hipcc release:
  * bench.py prints this string next to its numbers) */

@@ -90,7 +90,7 @@ extern "C" int64_t s2d_rulebook_sort_chunk_rows(int64_t n) {
         const int64_t rows = atoll(e);
         if (rows >= 16) return rows;
     }
-    const RgPlan p = rg_plan(n, 27, 64, 64);
+    const RgPlan p = rg_plan(n, 27, 128, 128);
     return (int64_t)(xcd_grid(p.grid) / S2D_XCDS) * p.tiles_per_block * 16;
 }
 

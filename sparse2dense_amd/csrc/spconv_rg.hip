@@ -551,8 +551,8 @@ static int rg_launch(const RgPlan &p, const __bf16 *in, int64_t n_in, const __bf
     return S2D_OK;
 }
 
-// rows grouped by neighbour mask (csrc/rulebook_sort.hip): one plan shape (two tiles per wave, eight waves), 64 -> 64 and 128 -> 128 - the
-// submanifold layers of the two wide stages
+// rows grouped by neighbour mask (csrc/rulebook_sort.hip): one plan shape (two tiles per wave, eight waves), 128 -> 128 - the
+// submanifold layers of the widest stage
 template <int CIN, int COUT>
 static int rg_launch_sorted(const RgPlan &p, const __bf16 *in, int64_t n_in, const __bf16 *wpack, const float *bias, const int32_t *nbr_perm,
                             const int32_t *perm, const uint32_t *pmask, int n_out, int kvol, __bf16 *out, float *stats, hipStream_t st) {
@@ -600,7 +600,9 @@ template <int CIN>
 static int rg_dispatch_cout(int cout, const RgPlan &p, const __bf16 *in, int64_t n_in, const __bf16 *wpack, const float *bias, const int32_t *nbr,
                             int n_out, int kvol, __bf16 *out, float *stats, hipStream_t st) {
     switch (cout) {
-        case 64: return rg_dispatch_plan<CIN, 64>(p, in, n_in, wpack, bias, nbr, n_out, kvol, out, stats, st);
+        case 64:   // 64 -> 64 stays on the LDS-staged kernel (use_rg in spconv_s16.hip)
+            if constexpr (CIN != 64) return rg_dispatch_plan<CIN, 64>(p, in, n_in, wpack, bias, nbr, n_out, kvol, out, stats, st);
+            break;
         case 128: return rg_dispatch_plan<CIN, 128>(p, in, n_in, wpack, bias, nbr, n_out, kvol, out, stats, st);
     }
     return S2D_ERR_UNSUPPORTED;
@@ -618,7 +620,7 @@ int rg_run(const void *in_feat, int64_t n_in, const void *packed_weight, const f
     return S2D_ERR_UNSUPPORTED;
 }
 
-bool rg_sorted_supported(int kvol, int cin, int cout) { return kvol == 27 && cin == cout && (cin == 64 || cin == 128); }
+bool rg_sorted_supported(int kvol, int cin, int cout) { return kvol == 27 && cin == 128 && cout == 128; }
 
 // the sorted-row launch: the plan is rg_plan's tile count with the fixed (2, 8) shape, so stats_partial has rg_plan(...).grid rows as usual
 int rg_run_sorted(const void *in_feat, int64_t n_in, const void *packed_weight, const float *bias, const int32_t *nbr_perm, const int32_t *perm,
@@ -627,7 +629,6 @@ int rg_run_sorted(const void *in_feat, int64_t n_in, const void *packed_weight, 
     if (plan.mi != 2 || plan.waves != 8) return S2D_ERR_UNSUPPORTED;   // (S2D_RG_PLAN tuning override in force)
     const __bf16 *in = (const __bf16 *)in_feat, *wp = (const __bf16 *)packed_weight;
     __bf16 *out = (__bf16 *)out_feat;
-    if (cin == 64 && cout == 64) return rg_launch_sorted<64, 64>(plan, in, n_in, wp, bias, nbr_perm, perm, pmask, (int)n_out, kvol, out, stats_partial, st);
     if (cin == 128 && cout == 128) return rg_launch_sorted<128, 128>(plan, in, n_in, wp, bias, nbr_perm, perm, pmask, (int)n_out, kvol, out, stats_partial, st);
     return S2D_ERR_UNSUPPORTED;
 }

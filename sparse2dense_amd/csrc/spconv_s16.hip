@@ -316,7 +316,8 @@ size_t rg_packed_elems(int kvol, int cin, int cout);
 int rg_pack(const float *weight, int kvol, int cin, int cout, int transpose, int flip, void *packed, hipStream_t st);
 int rg_pack_pair(const float *weight, int kvol, int cin, int cout, int flip_dgrad, void *packed_fwd, void *packed_dgrad, hipStream_t st);
 void rg_set_trace(void *p);
-// sorted-row mode (see use_rg): initial value from S2D_RG_SORTED, changed by s2d_spconv_s16_set_sorted_rows
+// sorted-row mode (128 -> 128 only; it changes no plan and no weight image): initial value from S2D_RG_SORTED, changed by
+// s2d_spconv_s16_set_sorted_rows
 static int &g_sorted_rows_mode() {
     static int mode = (getenv("S2D_RG_SORTED") && atoi(getenv("S2D_RG_SORTED")) != 0) ? 1 : 0;
     return mode;
@@ -330,9 +331,7 @@ static bool use_rg(int cin, int cout) {
     // 64 -> 64 (48 vs 52 us) and narrower stay on the LDS-staged kernel.  r03 experiment: the register-gather template instantiated for
     // 32 channels (four offsets per 128-deep K-step): 32 -> 32 61 vs 56 us, 64 -> 32 62 vs 68 us - no case for it; tile heights of the
     // LDS kernel re-swept at the same time (S2D_S16_PLAN): 64 rows still beat 128 / 256 at every 16...64-channel shape
-    // r06: with the sorted-row form switched on (s2d_spconv_s16_set_sorted_rows: opt-in, it measured SLOWER - see csrc/rulebook_sort.hip) 64 -> 64
-    // runs on the register-gather kernel too: one weight image must serve the plain and the sorted launch of a layer
-    return v != 0 && cin >= 64 && cout >= 64 && (cin == 128 || cout == 128 || g_sorted_rows_mode() != 0);
+    return v != 0 && cin >= 64 && cout >= 64 && (cin == 128 || cout == 128);
 }
 bool rg_sorted_supported(int kvol, int cin, int cout);
 int rg_run_sorted(const void *in_feat, int64_t n_in, const void *packed_weight, const float *bias, const int32_t *nbr_perm, const int32_t *perm,

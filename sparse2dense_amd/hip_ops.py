@@ -649,19 +649,16 @@ def spconv_s16_run(feat, packed, kvol, cin, cout, bias, nbr, n_out, pair_count=N
     return (out, partial) if bn_stats else out
 
 
-# submanifold 64 -> 64 / 128 -> 128 layers over mask-sorted rows (csrc/rulebook_sort.hip).  OPT-IN (S2D_RG_SORTED=1 / set_sorted_rows): on the
+# submanifold 128 -> 128 layers over mask-sorted rows (csrc/rulebook_sort.hip).  OPT-IN (S2D_RG_SORTED=1 / set_sorted_rows): on the
 # benchmark scene it is 5-10 % slower than the plain kernel (profiles/r06_sparse_sorted_rows_ab.txt) - the gathers, not the MFMAs, bound it.
 SORTED_ROWS = os.environ.get("S2D_RG_SORTED", "0") not in ("0", "")
 
 
 def set_sorted_rows(on):
-    """switch the sorted-row form on / off in the library and here; returns the previous setting.  The 64 -> 64 layers change their weight
-    image with it, so every cached image is dropped."""
+    """switch the sorted-row form on / off in the library and here; returns the previous setting"""
     global SORTED_ROWS
-    from .dense2d import clear_pack_cache
     was = bool(_lib.load().s2d_spconv_s16_set_sorted_rows(int(bool(on))))
     SORTED_ROWS = bool(on)
-    clear_pack_cache()
     return was
 
 

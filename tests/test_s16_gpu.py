@@ -320,21 +320,12 @@ def test_rulebook_rows_sorted_by_neighbour_mask(n, kind):
     (128, 333, "mixed", 0.3), (64, 1, "centre", 0.0), (64, 40, "full", 0.5),
 ])
 def test_rg_kernel_over_mask_sorted_rows_matches_fp32_at_benchmark_row_counts(c, n, kind, p_drop):
-    """the sorted-row instantiations against an fp32 restatement on the device, every row, with and without the statistics epilogue,
-    and against the plain kernel's output (same packed image): the stored rows must be in the CANONICAL order"""
+    """the kernels that serve the shaped maps against an fp32 restatement on the device, every row, with and without the statistics
+    epilogue: the plain kernel at both widths (register-gather <128, 128>, LDS-staged 64 -> 64) and, at 128 channels, the sorted-row
+    instantiation too, also against the plain kernel's output (same packed image): the stored rows must be in the CANONICAL order"""
     from sparse2dense_amd import hip_ops as H
     torch.manual_seed(c + n)
     nbr = _shaped_map(n, _SHAPES[kind], seed=7 * n + c, p_drop=p_drop)
-    rb = _subm_rulebook(nbr)
-    was = H.set_sorted_rows(True)
-    try:
-        assert H.spconv_s16_sorted_ok(rb, 27, c, c, n)
-        _check_sorted_kernel(H, c, n, nbr, rb)
-    finally:
-        H.set_sorted_rows(was)
-
-
-def _check_sorted_kernel(H, c, n, nbr, rb):
     feat = torch.randn(n, c, device=DEV).to(torch.bfloat16)
     w = torch.randn(27, c, c, device=DEV) * 0.05
     bias = torch.randn(c, device=DEV)
@@ -344,31 +335,40 @@ def _check_sorted_kernel(H, c, n, nbr, rb):
         o = torch.nonzero(nbr[k] >= 0).squeeze(1)
         ref[o] += fr[nbr[k][o].long()] @ wr[k]
     packed, kv, ci, co = H.spconv_s16_pack(w, n)
-    # every launch, the plain one included, stores into its own NaN-filled, guarded buffer (a freed block handed back by the allocator
-    # would still hold the right answer)
+    # every launch stores into its own NaN-filled, guarded buffer (a freed block handed back by the allocator would still hold the right answer)
     from test_spconv_plans_gpu import run_plain, run_sorted
-    plain = run_plain(feat, packed, kv, ci, co, bias, nbr, n)[0].float()
-    bad = ((plain - ref).abs() > 1.2e-2 * ref.abs().max()).any(1)
-    assert int(bad.sum()) == 0, ("plain", int(bad.sum()), bad.nonzero().flatten()[:8].tolist())
-    for with_stats in (False, True):
-        r = run_sorted(feat, packed, kv, ci, co, bias, rb, with_stats)
+
+    def check(r, with_stats):
         out = r[0].float()
         bad = ((out - ref).abs() > 1.2e-2 * ref.abs().max()).any(1) | (~torch.isfinite(out)).any(1)
         assert int(bad.sum()) == 0, (with_stats, int(bad.sum()), bad.nonzero().flatten()[:8].tolist())
-        # same products, same fp32 accumulation order per row (offsets ascending in both kernels): the two kernels agree to the last bf16 ulp
-        assert float((out - plain).abs().max()) <= 8e-3 * float(ref.abs().max())
         if with_stats:
             part = r[1].double().sum(0)
             o64 = r[0].double()
             assert torch.allclose(part[0], o64.sum(0), rtol=1e-4, atol=1e-2) and torch.allclose(part[1], (o64 * o64).sum(0), rtol=1e-4, atol=1e-2)
+        return out
+
+    plain = [check(run_plain(feat, packed, kv, ci, co, bias, nbr, n, with_stats), with_stats) for with_stats in (False, True)][0]
+    if c != 128:   # the sorted-row form exists for 128 -> 128 only
+        return
+    rb = _subm_rulebook(nbr)
+    was = H.set_sorted_rows(True)
+    try:
+        assert H.spconv_s16_sorted_ok(rb, 27, c, c, n)
+        for with_stats in (False, True):
+            out = check(run_sorted(feat, packed, kv, ci, co, bias, rb, with_stats), with_stats)
+            # same products, same fp32 accumulation order per row (offsets ascending in both kernels): the two kernels agree to the last bf16 ulp
+            assert float((out - plain).abs().max()) <= 8e-3 * float(ref.abs().max())
+    finally:
+        H.set_sorted_rows(was)
 
 
 def test_sparse_conv_layer_uses_the_sorted_rows_and_matches_the_plain_kernel():
     """spconv.SubMConv3d in the bf16-storage mode: forward and data gradient through the sorted-row kernel == through the plain one
-    (S2D_RG_SORTED=0 path), 64 channels"""
+    (S2D_RG_SORTED=0 path), 128 channels"""
     from sparse2dense_amd import hip_ops as H
     from sparse2dense_amd.spconv import _SparseConvFn
-    n, c = 20000, 64
+    n, c = 20000, 128
     nbr = _shaped_map(n, _SHAPES["mixed"], seed=5, p_drop=0.1)
     rb = _subm_rulebook(nbr)
     torch.manual_seed(1)

@@ -1,5 +1,5 @@
 """Sparse-conv kernel over mask-sorted rows (csrc/rulebook_sort.hip + spconv_rg_kernel<..., SORTED>) against the plain kernel on the bench
-scene's REAL rulebooks (4 x 150 k points): 64 -> 64 at stage 2, 128 -> 128 at stage 3, forward shape (= data-gradient shape).
+scene's REAL rulebooks (4 x 150 k points): 128 -> 128 at stage 3, forward shape (= data-gradient shape).
     python tools/mask_sort_kernel_bench.py            # S2D_RG_SORT_CHUNKS=1: global sort instead of XCD-local chunks
 Prints per stage: rows, pairs, R/(27 N), active (workgroup, offset) and (tile, offset) fractions of the sorted order, the sort's own time,
 both kernels' times and algorithmic fractions of the bf16 MFMA peak (2.5 PFLOP/s)."""
@@ -13,7 +13,7 @@ from sparse2dense_amd import _lib, hip_ops as H, waymo_configs
 from sparse2dense_amd.data import SyntheticFrames, attach_geometry
 from sparse2dense_amd.registry import build_detector
 
-H.set_sorted_rows(True)   # (opt-in mode: also puts 64 -> 64 on the register-gather weight image, for both kernels timed here)
+H.set_sorted_rows(True)
 dev = torch.device("cuda:0")
 model = build_detector(waymo_configs.s2d_student()).to(dev)
 frames = SyntheticFrames(4, n_points=150000, seed=20240928, distill=True, device=dev, beam_jitter=2.5e-3)
@@ -35,7 +35,7 @@ def timeit(fn, n=30):
 
 
 out = {}
-for key, c in (("res2", 64), ("res3", 128)):
+for key, c in (("res3", 128),):   # (the 64 -> 64 sorted kernel of stage 2 was removed: profiles/r06_sparse_sorted_rows_ab.txt has its numbers)
     rb = plan[key]
     n = int(rb.n_out)
     pairs = int(rb.pair_count.sum())
