@@ -171,6 +171,13 @@ size_t s2d_spconv_wgrad_workspace_bytes(int64_t n_out, int kvol, int cin, int co
 int s2d_spconv_wgrad_f32(const float *in_feat, int64_t n_in, const float *dout, const int32_t *nbr,
                          int64_t n_out, int kvol, int cin, int cout, float *dweight, void *ws,
                          size_t ws_bytes, s2d_stream_t stream);
+/* The launch plan of a weight-gradient entry for these sizes, no device work (tests, tools): mode 0
+ * s2d_spconv_wgrad_f32, 1 s2d_spconv_wgrad_bf16, 2 s2d_spconv_s16_wgrad.  out = {kernel, n_split,
+ * rows_per_split, grid_y, wrow}; kernel 0 fp32 MFMA, 1 bf16 MFMA with register-assembled fragments,
+ * 2 bf16 transpose-read, 3 workgroup-cooperative 128-channel, 4 VALU.  The plan, and with it the
+ * workspace query above, follows S2D_WGRAD_TR / S2D_WGRAD_COOP / S2D_WGRAD_WAVES, which are read on
+ * every call. */
+int s2d_spconv_wgrad_plan(int mode, int64_t n_out, int kvol, int cin, int cout, int32_t out[5]);
 
 /* same contract, MFMA inputs rounded to bf16 (fp32 accumulate); channel counts that the matrix path
  * does not cover fall back to the fp32 kernels inside. */

@@ -101,6 +101,8 @@ SIGNATURES = {
     "s2d_spconv_fwd_bf16": (ctypes.c_int, [c_f32p, ctypes.c_int64, ctypes.c_void_p, c_f32p, c_i32p, ctypes.c_int64,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
     "s2d_spconv_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "s2d_spconv_wgrad_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int32)]),
     "s2d_spconv_wgrad_f32": (ctypes.c_int, [c_f32p, ctypes.c_int64, c_f32p, c_i32p, ctypes.c_int64, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p, ctypes.c_size_t,
                                             ctypes.c_void_p]),
@@ -549,10 +551,12 @@ def load():
     # - ~150 ctypes round trips of 3-5 us per training step on the launch thread.  They depend on their integer arguments and on
     # environment switches the library reads once, so the answers are memoised per argument tuple.  (Not the sparse bf16-storage
     # kernels' queries: they follow S2D_RG_PLAN / S2D_S16_PLAN, which the library reads again on every call, and *_sorted_supported
-    # the sorted-row switch.)
+    # the sorted-row switch.  Not s2d_spconv_wgrad_workspace_bytes either: it follows S2D_WGRAD_TR / _COOP / _WAVES, read on every
+    # call, and its n_out differs on every training step, so its cache was never hit and only grew.  s2d_spconv_wgrad_plan takes a
+    # pointer and is not a candidate.)
     _int_types = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t)
     for name, (res, args) in SIGNATURES.items():
-        pure = name.endswith(("_workspace_bytes", "_supported", "_stats_tiles", "_tile_rows", "_packed_elems")) and "sort" not in name and "spconv_s16" not in name
+        pure = name.endswith(("_workspace_bytes", "_supported", "_stats_tiles", "_tile_rows", "_packed_elems")) and "sort" not in name and "spconv_s16" not in name and name != "s2d_spconv_wgrad_workspace_bytes"
         if pure and args and all(a in _int_types for a in args):
             setattr(lib, name, _memoised(getattr(lib, name)))
     _lib = lib

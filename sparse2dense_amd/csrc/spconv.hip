@@ -836,12 +836,11 @@ struct WgradPlan {
 };
 
 // mode: 0 fp32 MFMA, 1 bf16 MFMA on fp32 storage, 2 bf16 MFMA on bf16 storage (one per C-ABI entry point)
+// The three tuning hooks are read on every call (as rg_plan reads S2D_RG_PLAN): one process can sweep them, and three getenv calls are
+// nothing beside a kernel launch.
 static int wgrad_tr_override() {   // S2D_WGRAD_TR=0/1 forces the register-assembled / transpose-read bf16-storage kernel (A/B runs)
-    static const int v = [] {
-        const char *e = getenv("S2D_WGRAD_TR");
-        return e ? (e[0] == '1' ? 1 : 0) : 2;
-    }();
-    return v;
+    const char *e = getenv("S2D_WGRAD_TR");
+    return e ? (e[0] == '1' ? 1 : 0) : 2;
 }
 
 static WgradPlan wgrad_plan(int mode, int64_t n_out, int kvol, int cin, int cout) {
@@ -852,7 +851,8 @@ static WgradPlan wgrad_plan(int mode, int64_t n_out, int kvol, int cin, int cout
     // measured (r01, bench scene): the transpose-read kernel wins for cin <= 64 (16->16 144 -> 97 us ... 64->128 81 -> 58 us,
     // launch + reduce included) and loses at cin = 128 (120 -> 131 us: four waves each re-gather the 256-byte rows)
     p.tr = mode == 2 && p.mfma && (tr_pref == 1 || (tr_pref == 2 && cin <= 64));
-    static const int coop_env = [] { const char *e = getenv("S2D_WGRAD_COOP"); return e ? atoi(e) : 1; }();
+    const char *coop_e = getenv("S2D_WGRAD_COOP");
+    const int coop_env = coop_e ? atoi(coop_e) : 1;
     p.coop = mode == 2 && !p.tr && coop_env && cin == 128 && (cout == 128 || cout == 64);
     int vb = cout >= 32 ? 2 : 1;
     int wco = p.mfma ? cout / (16 * vb) : 1;
@@ -864,7 +864,8 @@ static WgradPlan wgrad_plan(int mode, int64_t n_out, int kvol, int cin, int cout
     p.wrow = p.mfma ? 4 / wco : 1;
     if (p.coop) p.wrow = 1;
     // aim at ~2048 waves in flight, at least 256 rows per split
-    static const int waves_env = [] { const char *e = getenv("S2D_WGRAD_WAVES"); return e ? atoi(e) : 0; }();
+    const char *waves_e = getenv("S2D_WGRAD_WAVES");
+    const int waves_env = waves_e ? atoi(waves_e) : 0;
     const int want_waves = waves_env > 0 ? waves_env : 2048;
     // rounded DOWN: the 128-channel kernel (174 VGPRs) fits two workgroups per CU = 512 on the chip, and 27 x 19 = 513
     // workgroups ran as two rounds
@@ -965,6 +966,20 @@ extern "C" size_t s2d_spconv_wgrad_workspace_bytes(int64_t n_out, int kvol, int 
         need = b > need ? b : need;
     }
     return align_up(need, 256);
+}
+
+// what a launch of entry `mode` (0 s2d_spconv_wgrad_f32, 1 s2d_spconv_wgrad_bf16, 2 s2d_spconv_s16_wgrad) with these sizes does, no device work:
+// out = {kernel id, n_split, rows_per_split, grid_y, wrow}; kernel id 0 spconv_wgrad_mfma, 1 spconv_wgrad_bf16, 2 spconv_wgrad_s16_tr,
+// 3 spconv_wgrad_s16_coop128, 4 spconv_wgrad_valu
+extern "C" int s2d_spconv_wgrad_plan(int mode, int64_t n_out, int kvol, int cin, int cout, int32_t out[5]) {
+    S2D_CHECK_ARG(mode >= 0 && mode <= 2 && n_out >= 0 && n_out < 0x7fffffff && kvol > 0 && cin > 0 && cout > 0 && out, "spconv_wgrad_plan: bad argument");
+    const WgradPlan p = wgrad_plan(mode, n_out, kvol, cin, cout);
+    out[0] = !p.mfma ? 4 : p.coop ? 3 : p.tr ? 2 : mode == 0 ? 0 : 1;
+    out[1] = p.n_split;
+    out[2] = p.rows_per_split;
+    out[3] = p.grid_y;
+    out[4] = p.wrow;
+    return S2D_OK;
 }
 
 static int wgrad_impl(int mode, const float *in_feat, int64_t n_in, const float *dout, const int32_t *nbr, int64_t n_out, int kvol,
