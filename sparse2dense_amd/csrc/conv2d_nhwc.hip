@@ -824,23 +824,54 @@ extern "C" int s2d_conv2d_pack_batch_bf16(int n, const float *const *weights, co
 }
 
 // ---- launch plan --------------------------------------------------------------------------------------------------
-static int conv_env_int(const char *name) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
+// One function (conv_plan) decides kernel family, column-block width, rows per tile, ring depth and grid of every entry below; the
+// launchers, the *_stats_tiles / *_tile_rows / *_bnbwd_supported queries and the report s2d_conv2d_plan (include/s2d_debug.h) all read
+// it, so what is reported is what is launched.  The A/B switches S2D_CONV_BM / S2D_CONV_NS / S2D_CONV1X1 are read from the environment
+// at first use into file-level values that s2d_conv2d_debug_force can override afterwards (tests sweep every instantiation in one
+// process); S2D_CONV_SHARED_A is read on every call, as before, unless forced.
+static int g_conv_bm = 0;          // 64 / 96 / 128: forced tile height of the k32 kernel; anything else: the cost model
+static int g_conv_ns = 0;          // 0 / 32: the 32-deep kernel; 2 / 3 / 4: the 64-deep ring of that depth
+static int g_conv1x1_k64 = 0;      // 1: the 1x1 launches take the 64-deep double buffer
+static int g_conv_shared_a = -1;   // -1: S2D_CONV_SHARED_A / the default rule; 0 / 1: forced
+static int conv_env_bm() { const char *e = getenv("S2D_CONV_BM"); return e ? atoi(e) : 0; }
+static int conv_env_ns() { const char *e = getenv("S2D_CONV_NS"); return e ? atoi(e) : 0; }
+static int conv_env_1x1_k64() { const char *e = getenv("S2D_CONV1X1"); return e && e[0] == 'k' && e[1] == '6'; }
+static void conv_switches_init() {
+    static const bool once = [] {
+        g_conv_bm = conv_env_bm();
+        g_conv_ns = conv_env_ns();
+        g_conv1x1_k64 = conv_env_1x1_k64();
+        return true;
+    }();
+    (void)once;
 }
+
+extern "C" int s2d_conv2d_debug_force(int bm, int ns, int shared_a, int conv1x1_k64) {
+    S2D_CHECK_ARG((bm == -1 || bm == 64 || bm == 96 || bm == 128) && (ns == -1 || ns == 32 || (ns >= 2 && ns <= 4)) &&
+                      (shared_a >= -1 && shared_a <= 1) && (conv1x1_k64 >= -1 && conv1x1_k64 <= 1),
+                  "conv2d_debug_force: bm -1/64/96/128, ns -1/32/2/3/4, shared_a -1/0/1, conv1x1_k64 -1/0/1");
+    conv_switches_init();
+    g_conv_bm = bm == -1 ? conv_env_bm() : bm;
+    g_conv_ns = ns == -1 ? conv_env_ns() : ns;
+    g_conv_shared_a = shared_a;
+    g_conv1x1_k64 = conv1x1_k64 == -1 ? conv_env_1x1_k64() : conv1x1_k64;
+    return S2D_OK;
+}
+
 static bool conv_use_shared_a(int cin, int bn, int pad, int stride) {
     // tap-shared A tile: measured on MI355X (r01) it wins where the A tile dominates the staged bytes (64-wide column
     // blocks with many input channels: 512->64 196 -> 141 us) and is neutral-to-slightly-slower at 128-wide blocks.
     // S2D_CONV_SHARED_A=0/1 forces the choice for A/B runs.
+    if (pad != 1 || stride != 1) return false;
+    if (g_conv_shared_a >= 0) return g_conv_shared_a == 1;
     const char *force = getenv("S2D_CONV_SHARED_A");
-    return pad == 1 && stride == 1 && (force ? force[0] == '1' : (bn == 64 && cin >= 128));
+    return force ? force[0] == '1' : (bn == 64 && cin >= 128);
 }
-static bool conv_use_k32(int bn) {
+static bool conv_use_k32() {
     // the 32-deep / 3-slot-ring kernel is the default for both column-block widths (64-wide blocks: 64->64@4x188^2 26 us
     // against 30 us on the 64-deep double buffer since the cursor rewrite); S2D_CONV_NS=2/3/4 forces the 64-deep variants
-    static const int ns_env = conv_env_int("S2D_CONV_NS");
-    (void)bn;
-    return ns_env == 32 || ns_env == 0;
+    conv_switches_init();
+    return g_conv_ns == 32 || g_conv_ns == 0;
 }
 // Output pixels per workgroup of the k32 kernel (128, 96 or 64).  The BEV launches are small against the chip (a
 // 256->256 conv on 4 x 94 x 94 pixels is 552 tiles of 128 x 128 for 768 resident workgroups).  Fitted to the measured
@@ -848,8 +879,8 @@ static bool conv_use_k32(int bn) {
 // shorter tiles pay while the launch is below one round of resident workgroups, taller ones amortise the per-step
 // overhead once it is above.
 static int conv_k32_rows(int64_t m, int col_blocks) {
-    static const int force = conv_env_int("S2D_CONV_BM");
-    if (force == 64 || force == 96 || force == 128) return force;
+    conv_switches_init();
+    if (g_conv_bm == 64 || g_conv_bm == 96 || g_conv_bm == 128) return g_conv_bm;
     static int slots = 0;
     if (!slots) {
         int dev = 0, n = 0;
@@ -869,23 +900,94 @@ static int conv_k32_rows(int64_t m, int col_blocks) {
     }
     return best;
 }
-static int conv_tile_rows(int64_t m, int cin, int cout, int pad, int stride) {
-    const int bn = conv_bn(cout);
-    if (conv_use_shared_a(cin, bn, pad, stride) || !conv_use_k32(bn)) return 128;
-    return bn == 128 ? conv_k32_rows(m, cout / bn) : 128;
+// 1x1 launches take the 32-deep three-slot-ring kernel with one tap (three workgroups per CU; measured r03 on the nine 1x1 shapes of
+// the S2D module: 393 us against 514 us for the 64-deep double buffer, e.g. 256 -> 256 @ 4 x 188^2 44.8 vs 61.3 us); S2D_CONV1X1=k64
+// forces the older route.  Rows per workgroup follow conv_k32_rows (128-wide column blocks only), as for the 3x3 launches.
+static bool conv1x1_use_k32(int cin) {
+    conv_switches_init();
+    return !g_conv1x1_k64 && cin >= 128;   // (the k32 loop needs >= 4 sub-steps = 128 channels of one tap)
+}
+static bool convup_supported(int kc, int nc, int ks) {
+    return (ks == 3 || ks == 4) && s2d_conv2d3x3_supported(kc, nc) && (ks == 4 || kc >= 128);   // >= 4 sub-steps per class
+}
+
+enum ConvKind { CONV_3X3 = 0, CONV_3X3_BNBWD = 1, CONV_1X1 = 2, CONV_1X1_BNBWD = 3, CONV_UP = 4, CONV_4X4S2 = 5, CONV_2X2S2 = 6 };
+enum ConvFamily { CONV_K32 = 0, CONV_K64 = 1, CONV_SHARED_A = 2 };
+struct ConvPlan {
+    int family = CONV_K32, bn = 0, rows = 0, ns = 0;   // ns: ring depth (3 for the k32 kernel, 2 for the shared-A kernel)
+    unsigned gx = 0, gy = 0, gz = 0;
+    int64_t m = 0;        // rows of the implicit GEMM (UP: source-grid pixels, per parity class)
+    int64_t tiles = 0;    // statistics slabs = row tiles (UP: 4 classes x row tiles)
+    bool ok = false;      // geometry and channels are supported by the entry
+    bool bnbwd_ok = false;   // the batch-norm backward epilogue exists on this route
+};
+// (h, w) = the entry's own arguments: the input image, for CONV_UP the source grid.  pad / stride: 3x3 kinds only; ks: CONV_UP only.
+static ConvPlan conv_plan(int kind, int n, int h, int w, int cin, int cout, int pad, int stride, int ks) {
+    ConvPlan p;
+    int ho = 0, wo = 0;
+    bool geo = n > 0 && h > 0 && w > 0, chan = s2d_conv2d3x3_supported(cin, cout);
+    switch (kind) {
+    case CONV_3X3:
+    case CONV_3X3_BNBWD:
+        geo = geo && (pad == 0 || pad == 1) && (stride == 1 || stride == 2) && h + 2 * pad >= 3 && w + 2 * pad >= 3;
+        if (geo) { ho = (h + 2 * pad - 3) / stride + 1; wo = (w + 2 * pad - 3) / stride + 1; }
+        break;
+    case CONV_1X1:
+    case CONV_1X1_BNBWD: ho = h; wo = w; break;
+    case CONV_UP: ho = h; wo = w; chan = convup_supported(cin, cout, ks); break;
+    case CONV_4X4S2: geo = geo && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0; ho = h / 2; wo = w / 2; break;
+    case CONV_2X2S2: geo = geo && h >= 2 && w >= 2; ho = h / 2; wo = w / 2; break;
+    default: geo = false;
+    }
+    if (!geo) return p;
+    p.m = (int64_t)n * ho * wo;
+    p.bn = conv_bn(cout);
+    const int col_blocks = cout / p.bn;
+    p.rows = 128;
+    if (kind == CONV_3X3 || kind == CONV_3X3_BNBWD) {
+        if (conv_use_shared_a(cin, p.bn, pad, stride)) { p.family = CONV_SHARED_A; p.ns = 2; }
+        else if (!conv_use_k32()) { p.family = CONV_K64; p.ns = g_conv_ns; }
+        else { p.family = CONV_K32; }
+    } else if (kind == CONV_1X1 || kind == CONV_1X1_BNBWD) {
+        if (!conv1x1_use_k32(cin)) { p.family = CONV_K64; p.ns = 2; }
+    } else if (kind == CONV_2X2S2) {
+        p.family = CONV_K64; p.ns = 2;
+    }
+    if (p.family == CONV_K32) {
+        p.ns = 3;
+        if (p.bn == 128) p.rows = conv_k32_rows(kind == CONV_UP ? 4 * p.m : p.m, col_blocks);
+    }
+    const int64_t row_tiles = ceil_div(p.m, p.rows);
+    p.gx = xcd_grid(row_tiles);
+    p.gy = (unsigned)col_blocks;
+    p.gz = kind == CONV_UP ? 4 : 1;
+    p.tiles = (kind == CONV_UP ? 4 : 1) * row_tiles;
+    p.ok = chan;
+    p.bnbwd_ok = chan && p.family == CONV_K32 && (kind == CONV_1X1 || kind == CONV_1X1_BNBWD || ((kind == CONV_3X3 || kind == CONV_3X3_BNBWD) && stride == 1));
+    return p;
+}
+
+/* include/s2d_debug.h.  out = {family (0 k32, 1 64-deep ring, 2 shared-A), BN, rows per tile, NS, grid x, y, z, tiles} */
+extern "C" int s2d_conv2d_plan(int kind, int n, int h, int w, int cin, int cout, int pad, int stride, int ks, int32_t out[8]) {
+    S2D_CHECK_ARG(out, "conv2d_plan: null argument");
+    const ConvPlan p = conv_plan(kind, n, h, w, cin, cout, pad, stride, ks);
+    out[0] = p.family; out[1] = p.bn; out[2] = p.rows; out[3] = p.ns;
+    out[4] = (int32_t)p.gx; out[5] = (int32_t)p.gy; out[6] = (int32_t)p.gz; out[7] = (int32_t)p.tiles;
+    if (!p.ok || ((kind == CONV_3X3_BNBWD || kind == CONV_1X1_BNBWD) && !p.bnbwd_ok)) {
+        set_error("conv2d_plan: kind %d is not supported for %d x %d x %d, %d -> %d, pad %d, stride %d, ks %d", kind, n, h, w, cin, cout, pad, stride, ks);
+        return S2D_ERR_UNSUPPORTED;
+    }
+    return S2D_OK;
 }
 
 extern "C" int s2d_conv2d3x3_tile_rows(int n_img, int h, int w, int cin, int cout, int pad, int stride) {
-    if (!s2d_conv2d3x3_supported(cin, cout) || n_img <= 0 || h + 2 * pad < 3 || w + 2 * pad < 3 || stride < 1) return 0;
-    const int ho = (h + 2 * pad - 3) / stride + 1, wo = (w + 2 * pad - 3) / stride + 1;
-    return conv_tile_rows((int64_t)n_img * ho * wo, cin, cout, pad, stride);
+    const ConvPlan p = conv_plan(CONV_3X3, n_img, h, w, cin, cout, pad, stride, 3);
+    return p.ok ? p.rows : 0;
 }
 
 extern "C" int64_t s2d_conv2d3x3_stats_tiles(int n_img, int h, int w, int cin, int cout, int pad, int stride) {
-    if (!s2d_conv2d3x3_supported(cin, cout) || n_img <= 0 || h + 2 * pad < 3 || w + 2 * pad < 3 || stride < 1) return 0;
-    const int ho = (h + 2 * pad - 3) / stride + 1, wo = (w + 2 * pad - 3) / stride + 1;
-    const int64_t m = (int64_t)n_img * ho * wo;
-    return ceil_div(m, conv_tile_rows(m, cin, cout, pad, stride));
+    const ConvPlan p = conv_plan(CONV_3X3, n_img, h, w, cin, cout, pad, stride, 3);
+    return p.ok ? p.tiles : 0;
 }
 
 static int conv3x3_run(const void *x, const void *packed_weight, const float *bias, const void *zero_page, int n_img, int h, int w, int cin,
@@ -896,14 +998,13 @@ static int conv3x3_run(const void *x, const void *packed_weight, const float *bi
         set_error("conv2d3x3: unsupported channels %d -> %d", cin, cout);
         return S2D_ERR_UNSUPPORTED;
     }
-    const int ho = (h + 2 * pad - 3) / stride + 1, wo = (w + 2 * pad - 3) / stride + 1;
     S2D_CHECK_ARG(h + 2 * pad >= 3 && w + 2 * pad >= 3, "conv2d3x3: empty output");
-    const int64_t m = (int64_t)n_img * ho * wo;
+    const ConvPlan plan = conv_plan(bb.z ? CONV_3X3_BNBWD : CONV_3X3, n_img, h, w, cin, cout, pad, stride, 3);
     hipStream_t st = (hipStream_t)stream;
-    const int bn = conv_bn(cout);
-    const dim3 grid(xcd_grid(ceil_div(m, 128)), cout / bn), blk(256);
-    const bool shared_a = conv_use_shared_a(cin, bn, pad, stride);
-    if (bb.z && (shared_a || !conv_use_k32(bn))) {   // (callers ask s2d_conv2d3x3_bnbwd_supported first)
+    const int bn = plan.bn;
+    const dim3 grid(plan.gx, plan.gy, plan.gz), blk(256);
+    const bool shared_a = plan.family == CONV_SHARED_A;
+    if (bb.z && !plan.bnbwd_ok) {   // (callers ask s2d_conv2d3x3_bnbwd_supported first)
         set_error("conv2d3x3: the batch-norm backward epilogue needs the 32-deep kernel (%d -> %d, pad %d, stride %d)", cin, cout, pad, stride);
         return S2D_ERR_UNSUPPORTED;
     }
@@ -931,16 +1032,13 @@ static int conv3x3_run(const void *x, const void *packed_weight, const float *bi
         S2D_LAUNCH_CHECK();
         return S2D_OK;
     }
-    // ring depth of the LDS-DMA pipeline (S2D_CONV_NS=2/3/4 forces it for A/B runs)
-    static const int ns_env = [] { const char *e = getenv("S2D_CONV_NS"); return e ? atoi(e) : 0; }();
-    const int ns = (ns_env >= 2 && ns_env <= 4) ? ns_env : 2;
-    if (conv_use_k32(bn)) {   // 32-deep K-steps, 3-slot ring
+    if (plan.family == CONV_K32) {   // 32-deep K-steps, 3-slot ring
 #define S2D_CONV_K32(BN_, MI_)                                                                                                  \
-    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<BN_, MI_>), dim3(xcd_grid(ceil_div(m, 32 * MI_)), cout / bn), blk,         \
+    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<BN_, MI_>), grid, blk,                                                     \
                        3 * (size_t)(32 * MI_ * 64 + 64 * BN_), st, (const __bf16 *)x, (const __bf16 *)packed_weight, bias,      \
                        (const __bf16 *)zero_page, n_img, h, w, cin, cout, pad, stride, (__bf16 *)y, stats_partial, bb)
         if (bn == 128) {
-            const int rows = conv_k32_rows(m, cout / bn);
+            const int rows = plan.rows;
             if (rows == 128) S2D_CONV_K32(128, 4);
             else if (rows == 96) S2D_CONV_K32(128, 3);
             else S2D_CONV_K32(128, 2);
@@ -951,6 +1049,7 @@ static int conv3x3_run(const void *x, const void *packed_weight, const float *bi
         S2D_LAUNCH_CHECK();
         return S2D_OK;
     }
+    const int ns = plan.ns;   // ring depth of the LDS-DMA pipeline (S2D_CONV_NS=2/3/4 forces it for A/B runs)
     const size_t lds = (size_t)ns * (128 * 64 * 2 + 64 * bn * 2);
 #define S2D_CONV_LAUNCH(BN_, NS_)                                                                                         \
     do {                                                                                                                  \
@@ -983,9 +1082,7 @@ extern "C" int s2d_conv2d3x3_nhwc_bf16(const void *x, const void *packed_weight,
    bn_partial[tile][2][cout] receives its backward sums (sum g, sum g z; g = dY act'(z scale + shift)) - the slabs
    s2d_bn_partials_bwd_finalize_f32 folds.  Tiles as s2d_conv2d3x3_stats_tiles. */
 extern "C" int s2d_conv2d3x3_bnbwd_supported(int cin, int cout, int pad, int stride) {
-    if (!s2d_conv2d3x3_supported(cin, cout) || stride != 1) return 0;
-    const int bn = conv_bn(cout);
-    return !conv_use_shared_a(cin, bn, pad, stride) && conv_use_k32(bn);
+    return conv_plan(CONV_3X3_BNBWD, 1, 3, 3, cin, cout, pad, stride, 3).bnbwd_ok;   // (the route does not depend on the image size)
 }
 
 extern "C" int s2d_conv2d3x3_nhwc_bf16_bnbwd(const void *x, const void *packed_weight, const void *zero_page, int n_img, int h, int w, int cin,
@@ -1003,9 +1100,6 @@ extern "C" int s2d_conv2d3x3_nhwc_bf16_bnbwd(const void *x, const void *packed_w
 // at 47 -> 94 and 94 -> 188) and the backward of the RPN's stride-2 3x3 convs (rpn.py:126-133).  "up": source [n][h][w][kc] ->
 // [n][2h][2w][nc]; ks = 4: ConvTranspose2d(4,2,1) forward from its weight [kc][nc][4][4]; ks = 3: data gradient of
 // Conv2d(nc -> kc, 3, stride 2, pad 1) on a [2h][2w] input from its weight [kc][nc][3][3].
-static bool convup_supported(int kc, int nc, int ks) {
-    return (ks == 3 || ks == 4) && s2d_conv2d3x3_supported(kc, nc) && (ks == 4 || kc >= 128);   // >= 4 sub-steps per class
-}
 extern "C" int s2d_convup_supported(int kc, int nc, int ks) { return convup_supported(kc, nc, ks); }
 
 extern "C" int s2d_convup_pack_weights_bf16(const float *weight, int kc, int nc, int ks, void *packed, s2d_stream_t stream) {
@@ -1021,12 +1115,9 @@ extern "C" int s2d_convup_pack_weights_bf16(const float *weight, int kc, int nc,
     return S2D_OK;
 }
 
-static int convup_rows(int64_t m, int nc) { return conv_bn(nc) == 128 ? conv_k32_rows(4 * m, nc / 128) : 128; }
-
 extern "C" int64_t s2d_convup_stats_tiles(int n_img, int h, int w, int kc, int nc, int ks) {
-    if (!convup_supported(kc, nc, ks) || n_img <= 0 || h <= 0 || w <= 0) return 0;
-    const int64_t m = (int64_t)n_img * h * w;
-    return 4 * ceil_div(m, convup_rows(m, nc));
+    const ConvPlan p = conv_plan(CONV_UP, n_img, h, w, kc, nc, 1, 2, ks);
+    return p.ok ? p.tiles : 0;
 }
 
 extern "C" int s2d_convup_nhwc_bf16(const void *x, const void *packed_weight, const float *bias, const void *zero_page, int n_img, int h,
@@ -1036,23 +1127,24 @@ extern "C" int s2d_convup_nhwc_bf16(const void *x, const void *packed_weight, co
         set_error("convup: unsupported %d -> %d, kernel %d", kc, nc, ks);
         return S2D_ERR_UNSUPPORTED;
     }
-    const int64_t m = (int64_t)n_img * h * w;
-    const int rows = convup_rows(m, nc);
+    const ConvPlan plan = conv_plan(CONV_UP, n_img, h, w, kc, nc, 1, 2, ks);
+    const int rows = plan.rows;
+    const dim3 grid(plan.gx, plan.gy, plan.gz);
     hipStream_t st = (hipStream_t)stream;
-    if (conv_bn(nc) == 64) {   // 64-wide column blocks (the pillar S2D module's 64-channel decoder, pillar_encoder.py:337-394)
+    if (plan.bn == 64) {   // 64-wide column blocks (the pillar S2D module's 64-channel decoder, pillar_encoder.py:337-394)
         if (ks == 4)
-            hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<64, 4, 4, true>), dim3(xcd_grid(ceil_div(m, 128)), nc / 64, 4), dim3(256),
+            hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<64, 4, 4, true>), grid, dim3(256),
                                3 * (size_t)(128 * 64 + 64 * 64), st, (const __bf16 *)x, (const __bf16 *)packed_weight, bias,
                                (const __bf16 *)zero_page, n_img, h, w, kc, nc, 1, 2, (__bf16 *)y, stats_partial, BnBwd{});
         else
-            hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<64, 4, 3, true>), dim3(xcd_grid(ceil_div(m, 128)), nc / 64, 4), dim3(256),
+            hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<64, 4, 3, true>), grid, dim3(256),
                                3 * (size_t)(128 * 64 + 64 * 64), st, (const __bf16 *)x, (const __bf16 *)packed_weight, bias,
                                (const __bf16 *)zero_page, n_img, h, w, kc, nc, 1, 2, (__bf16 *)y, stats_partial, BnBwd{});
         S2D_LAUNCH_CHECK();
         return S2D_OK;
     }
 #define S2D_CONVUP(MI_, KS_)                                                                                                       \
-    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<128, MI_, KS_, true>), dim3(xcd_grid(ceil_div(m, 32 * MI_)), nc / 128, 4),     \
+    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<128, MI_, KS_, true>), grid,                                                   \
                        dim3(256), 3 * (size_t)(32 * MI_ * 64 + 64 * 128), st, (const __bf16 *)x, (const __bf16 *)packed_weight,    \
                        bias, (const __bf16 *)zero_page, n_img, h, w, kc, nc, 1, 2, (__bf16 *)y, stats_partial, BnBwd{})
     if (ks == 4) {
@@ -1088,18 +1180,19 @@ extern "C" int s2d_conv2d4x4s2_nhwc_bf16(const void *x, const void *packed_weigh
         set_error("conv2d4x4s2: unsupported channels %d -> %d", cin, cout);
         return S2D_ERR_UNSUPPORTED;
     }
-    const int64_t m = (int64_t)n_img * (h / 2) * (w / 2);
+    const ConvPlan plan = conv_plan(CONV_4X4S2, n_img, h, w, cin, cout, 1, 2, 4);
+    const dim3 grid(plan.gx, plan.gy, plan.gz);
     hipStream_t st = (hipStream_t)stream;
-    if (conv_bn(cout) == 64) {
-        hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<64, 4, 4, false>), dim3(xcd_grid(ceil_div(m, 128)), cout / 64), dim3(256),
+    if (plan.bn == 64) {
+        hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<64, 4, 4, false>), grid, dim3(256),
                            3 * (size_t)(128 * 64 + 64 * 64), st, (const __bf16 *)x, (const __bf16 *)packed_weight, (const float *)nullptr,
                            (const __bf16 *)zero_page, n_img, h, w, cin, cout, 1, 2, (__bf16 *)y, (float *)nullptr, BnBwd{});
         S2D_LAUNCH_CHECK();
         return S2D_OK;
     }
-    const int rows = conv_k32_rows(m, cout / 128);
+    const int rows = plan.rows;
 #define S2D_CONV4(MI_)                                                                                                             \
-    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<128, MI_, 4, false>), dim3(xcd_grid(ceil_div(m, 32 * MI_)), cout / 128),       \
+    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<128, MI_, 4, false>), grid,                                                    \
                        dim3(256), 3 * (size_t)(32 * MI_ * 64 + 64 * 128), st, (const __bf16 *)x, (const __bf16 *)packed_weight,    \
                        (const float *)nullptr, (const __bf16 *)zero_page, n_img, h, w, cin, cout, 1, 2, (__bf16 *)y, (float *)nullptr, BnBwd{})
     if (rows == 128) S2D_CONV4(4); else if (rows == 96) S2D_CONV4(3); else S2D_CONV4(2);
@@ -1128,20 +1221,8 @@ extern "C" int s2d_conv2d1x1_pack_weights_bf16(const float *weight, int cin, int
     return S2D_OK;
 }
 
-// 1x1 launches take the 32-deep three-slot-ring kernel with one tap (three workgroups per CU; measured r03 on the nine 1x1 shapes of
-// the S2D module: 393 us against 514 us for the 64-deep double buffer, e.g. 256 -> 256 @ 4 x 188^2 44.8 vs 61.3 us); S2D_CONV1X1=k64
-// forces the older route.  Rows per workgroup follow conv_k32_rows (128-wide column blocks only), as for the 3x3 launches.
-static bool conv1x1_use_k32(int cin) {
-    static const bool k64 = [] { const char *e = getenv("S2D_CONV1X1"); return e && e[0] == 'k' && e[1] == '6'; }();
-    return !k64 && cin >= 128;
-}
-static int conv1x1_rows(int64_t m, int cin, int cout) {
-    return conv1x1_use_k32(cin) && conv_bn(cout) == 128 ? conv_k32_rows(m, cout / 128) : 128;
-}
-
 extern "C" int64_t s2d_conv2d1x1_stats_tiles(int n_img, int h, int w, int cin, int cout) {
-    const int64_t m = (int64_t)n_img * h * w;
-    return ceil_div(m, conv1x1_rows(m, cin, cout));
+    return conv_plan(CONV_1X1, n_img, h, w, cin, cout, 0, 1, 1).tiles;
 }
 
 static int conv1x1_run(const void *x, const void *packed_weight, const float *bias, const void *zero_page, int n_img, int h, int w, int cin,
@@ -1151,22 +1232,22 @@ static int conv1x1_run(const void *x, const void *packed_weight, const float *bi
         set_error("conv2d1x1: unsupported channels %d -> %d", cin, cout);
         return S2D_ERR_UNSUPPORTED;
     }
-    const int64_t m = (int64_t)n_img * h * w;
-    const int bn = conv_bn(cout);
-    const dim3 grid(xcd_grid(ceil_div(m, 128)), cout / bn), blk(256);
+    const ConvPlan plan = conv_plan(bb.z ? CONV_1X1_BNBWD : CONV_1X1, n_img, h, w, cin, cout, 0, 1, 1);
+    const int bn = plan.bn;
+    const dim3 grid(plan.gx, plan.gy, plan.gz), blk(256);
     const size_t lds = (size_t)2 * (128 * 64 * 2 + 64 * bn * 2);
     hipStream_t st = (hipStream_t)stream;
-    if (bb.z && !conv1x1_use_k32(cin)) {
+    if (bb.z && !plan.bnbwd_ok) {
         set_error("conv2d1x1: the batch-norm backward epilogue needs the 32-deep kernel (%d -> %d)", cin, cout);
         return S2D_ERR_UNSUPPORTED;
     }
-    if (conv1x1_use_k32(cin)) {
+    if (plan.family == CONV_K32) {
 #define S2D_CONV1_K32(BN_, MI_)                                                                                                    \
-    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<BN_, MI_, 1, false>), dim3(xcd_grid(ceil_div(m, 32 * MI_)), cout / bn), blk,   \
+    hipLaunchKernelGGL((conv3x3_k32_nhwc_bf16_kernel<BN_, MI_, 1, false>), grid, blk,                                               \
                        3 * (size_t)(32 * MI_ * 64 + 64 * BN_), st, (const __bf16 *)x, (const __bf16 *)packed_weight, bias,         \
                        (const __bf16 *)zero_page, n_img, h, w, cin, cout, 0, 1, (__bf16 *)y, stats_partial, bb)
         if (bn == 128) {
-            const int rows = conv1x1_rows(m, cin, cout);
+            const int rows = plan.rows;
             if (rows == 128) S2D_CONV1_K32(128, 4); else if (rows == 96) S2D_CONV1_K32(128, 3); else S2D_CONV1_K32(128, 2);
         } else {
             S2D_CONV1_K32(64, 4);
@@ -1197,7 +1278,7 @@ extern "C" int s2d_conv2d1x1_nhwc_bf16(const void *x, const void *packed_weight,
     return conv1x1_run(x, packed_weight, bias, zero_page, n_img, h, w, cin, cout, y, stats_partial, BnBwd{}, stream);
 }
 
-extern "C" int s2d_conv2d1x1_bnbwd_supported(int cin, int cout) { return s2d_conv2d3x3_supported(cin, cout) && conv1x1_use_k32(cin); }
+extern "C" int s2d_conv2d1x1_bnbwd_supported(int cin, int cout) { return conv_plan(CONV_1X1_BNBWD, 1, 1, 1, cin, cout, 0, 1, 1).bnbwd_ok; }
 
 /* 1x1 data gradient with the batch-norm backward epilogue (see s2d_conv2d3x3_nhwc_bf16_bnbwd); tiles as s2d_conv2d1x1_stats_tiles */
 extern "C" int s2d_conv2d1x1_nhwc_bf16_bnbwd(const void *x, const void *packed_weight, const void *zero_page, int n_img, int h, int w, int cin,
@@ -1226,7 +1307,7 @@ extern "C" int s2d_conv2d2x2s2_pack_weights_bf16(const float *weight, int cin, i
     return S2D_OK;
 }
 
-extern "C" int64_t s2d_conv2d2x2s2_stats_tiles(int n_img, int h, int w) { return ceil_div((int64_t)n_img * (h / 2) * (w / 2), 128); }
+extern "C" int64_t s2d_conv2d2x2s2_stats_tiles(int n_img, int h, int w) { return conv_plan(CONV_2X2S2, n_img, h, w, 64, 64, 0, 2, 2).tiles; }
 
 extern "C" int s2d_conv2d2x2s2_nhwc_bf16(const void *x, const void *packed_weight, const float *bias, const void *zero_page, int n_img, int h,
                                          int w, int cin, int cout, void *y, float *stats_partial, s2d_stream_t stream) {
@@ -1235,9 +1316,9 @@ extern "C" int s2d_conv2d2x2s2_nhwc_bf16(const void *x, const void *packed_weigh
         set_error("conv2d2x2s2: unsupported channels %d -> %d", cin, cout);
         return S2D_ERR_UNSUPPORTED;
     }
-    const int64_t m = (int64_t)n_img * (h / 2) * (w / 2);
-    const int bn = conv_bn(cout);
-    const dim3 grid(xcd_grid(ceil_div(m, 128)), cout / bn), blk(256);
+    const ConvPlan plan = conv_plan(CONV_2X2S2, n_img, h, w, cin, cout, 0, 2, 2);
+    const int bn = plan.bn;
+    const dim3 grid(plan.gx, plan.gy, plan.gz), blk(256);
     const size_t lds = (size_t)2 * (128 * 64 * 2 + 64 * bn * 2);
     hipStream_t st = (hipStream_t)stream;
 #define S2D_CONV2_LAUNCH(BN_)                                                                                             \

@@ -77,6 +77,37 @@ def test_launch_plans_of_the_dense_conv_kernels(lib):
     assert lib.s2d_comm_ranks() == 0                                       # no communicator without a process group
 
 
+def test_default_conv2d_plans_are_the_pinned_ones(lib):
+    """With nothing forced, the plan report s2d_conv2d_plan (the function the launchers read) equals the launch arithmetic of the commit
+    before the override entries existed, restated in tests/conv2d_ref.mirror_plan (conv_k32_rows cost model over 3 x CUs slots,
+    conv_use_shared_a, conv1x1_use_k32), for the benchmark's layer shapes (tools/conv_bm_bench.py).  No launch."""
+    import ctypes
+    import torch
+    import conv2d_ref as C
+    for name in ("S2D_CONV_BM", "S2D_CONV_NS", "S2D_CONV_SHARED_A", "S2D_CONV1X1"):
+        assert os.environ.get(name) is None, f"{name} is set: the library would not take its default plan"
+    cus = torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+    assert lib.s2d_conv2d_debug_force(-1, -1, -1, -1) == 0
+    shapes = [C.geo(C.K3, 4, 188, 188, 128, 128, 1, 1), C.geo(C.K3, 4, 188, 188, 64, 64, 1, 1), C.geo(C.K3, 4, 94, 94, 256, 256, 1, 1),
+              C.geo(C.K3, 4, 188, 188, 512, 64, 1, 1), C.geo(C.K3, 4, 188, 188, 256, 128, 1, 1), C.geo(C.K3, 4, 188, 188, 128, 256, 1, 1),
+              C.geo(C.K3, 4, 94, 94, 256, 512, 1, 1), C.geo(C.K3, 1, 188, 188, 128, 128, 1, 1), C.geo(C.K3, 4, 190, 190, 128, 256, 0, 2),
+              C.geo(C.K3, 4, 188, 188, 128, 256, 1, 2), C.geo(C.K3_BNBWD, 4, 188, 188, 128, 128, 1, 1), C.geo(C.K3_BNBWD, 4, 94, 94, 256, 256, 1, 1),
+              C.geo(C.K1, 4, 188, 188, 256, 256), C.geo(C.K1, 4, 188, 188, 256, 640), C.geo(C.K1, 4, 47, 47, 256, 1024),
+              C.geo(C.K1, 4, 47, 47, 1024, 256), C.geo(C.K1, 4, 188, 188, 64, 64), C.geo(C.K1_BNBWD, 4, 47, 47, 1024, 256),
+              C.geo(C.UP, 4, 47, 47, 256, 256, ks=4), C.geo(C.UP, 4, 94, 94, 256, 256, ks=4), C.geo(C.UP, 4, 94, 94, 256, 128, ks=3),
+              C.geo(C.UP, 4, 58, 58, 64, 64, ks=4), C.geo(C.K4S2, 4, 94, 94, 256, 256), C.geo(C.K4S2, 4, 188, 188, 256, 256),
+              C.geo(C.K2S2, 4, 376, 376, 64, 256), C.geo(C.K2S2, 4, 188, 188, 256, 256)]
+    out = (ctypes.c_int32 * 8)()
+    for g in shapes:
+        assert lib.s2d_conv2d_plan(g.kind, g.n, g.h, g.w, g.cin, g.cout, g.pad, g.stride, g.ks, out) == 0, (g, _lib.last_error())
+        assert C.Plan(*list(out)) == C.mirror_plan(g, cus), g
+    if cus == 256:   # the values themselves, for the three tile heights of the cost model and the two other kernel families
+        pinned = {0: (C.K32, 128, 128, 3, 1112, 1, 1, 1105), 2: (C.K32, 128, 96, 3, 376, 2, 1, 369), 3: (C.SHARED_A, 64, 128, 2, 1112, 1, 1, 1105),
+                  7: (C.K32, 128, 64, 3, 560, 1, 1, 553), 16: (C.K64, 64, 128, 2, 1112, 1, 1, 1105), 18: (C.K32, 128, 96, 3, 96, 2, 4, 372)}
+        for i, want in pinned.items():
+            assert tuple(C.mirror_plan(shapes[i], 256)) == want, (shapes[i], C.mirror_plan(shapes[i], 256))
+
+
 def test_ops_fail_loudly_on_cpu_tensors():
     import torch
     from sparse2dense_amd import hip_ops
