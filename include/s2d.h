@@ -1413,6 +1413,30 @@ int s2d_track_step(const float *boxes, const int64_t *labels, const float *score
                    const s2d_track_segment *segments, const s2d_track_label *label_table, int num_labels, int max_age, float score_thresh,
                    const double *ct_old, const double *tracking_old, const int32_t *meta_old, const int32_t *head_old, double *ct_new,
                    double *tracking_new, int32_t *meta_new, int32_t *head_new, int32_t *tracking_id, int32_t *active, s2d_stream_t stream);
+/* The same step on padded, device-counted rows, for callers that must not touch the host between predict and track (the output of
+ * s2d_predict_static_gather goes in as it lies) and for HIP-graph capture: ONE launch, the same association code.
+ *
+ * boxes [S][cap][9] fp32, labels int64 [S][cap], scores fp32 [S][cap], counts int32 [S] on the DEVICE: segment s owns rows
+ * s * cap .. s * cap + clamp(counts[s], 0, cap) - 1 and nothing behind them is read.  frames DEVICE [S] (112 bytes each): pose as above,
+ * stamp = this frame's timestamp in seconds, first, skip as above.  The time lag is formed on the device: first ? 0 : stamp - prev_stamp[s]
+ * in double; prev_stamp double [S] is state and takes the new stamp unless skip is set.
+ *
+ * State: the layout above twice - ct, tracking double [2][S][S2D_TRACK_MAX_TRACKS][2], meta int32 [2][S][S2D_TRACK_MAX_TRACKS][4], head
+ * int32 [2][S][2] - plus parity int32 [S]: half parity[s] holds segment s's current list; a step reads it, writes the other half and
+ * stores parity[s] = 1 - parity[s].  A skipped segment keeps parity, state and prev_stamp untouched (no copy).  Zero everything once.
+ * tracking_id, active int32 [S][cap]: all cap rows are written at every call, -1 / 0 for filtered rows, for rows at or behind counts[s]
+ * and for every row of a skipped segment.  first, an empty frame (counts[s] == 0), the label table, score_thresh and max_age as above.
+ * Returns -1 before any HIP call for S outside 1..64, cap outside 1..S2D_TRACK_MAX_DETS, cap * (max_age + 1) > S2D_TRACK_MAX_TRACKS
+ * (a segment's tracks never exceed the rows of its last max_age + 1 frames), num_labels outside 1..127 and null pointers. */
+typedef struct {
+    double pose[12];
+    double stamp;
+    int32_t first, skip;
+} s2d_track_frame;
+int s2d_track_step_static(const float *boxes, const int64_t *labels, const float *scores, const int32_t *counts, int num_segments, int cap,
+                          const s2d_track_frame *frames, const s2d_track_label *label_table, int num_labels, int max_age, float score_thresh,
+                          double *ct, double *tracking, int32_t *meta, int32_t *head, int32_t *parity, double *prev_stamp,
+                          int32_t *tracking_id, int32_t *active, s2d_stream_t stream);
 
 /* ---- detection AP evaluation (csrc/eval_ap.hip): the reference's KITTI-protocol evaluator (det3d/datasets/kitti/eval.py,
  * det3d/datasets/utils/eval.py, rotate_iou_gpu_eval of det3d/ops/nms/nms_gpu.py), every frame of a split in ONE launch per entry.

@@ -501,6 +501,9 @@ SIGNATURES = {
     # center-based tracker: every segment's step in one launch (csrc/tracking.hip)
     "s2d_track_step": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_float] + [ctypes.c_void_p] * 10 + [ctypes.c_void_p]),
+    # the same step on padded rows with device counts, device time lag and device buffer parity: capturable into a HIP graph
+    "s2d_track_step_static": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 8 + [ctypes.c_void_p]),
     # detection AP evaluation: overlaps, first-pass matching and the threshold sweep, one launch each for a whole split (csrc/eval_ap.hip)
     "s2d_eval_overlaps": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                          ctypes.c_void_p, ctypes.c_void_p]),

@@ -2,6 +2,9 @@
 tools/waymo_tracking/tracker.py:42-136) behind `transform_box` (tools/waymo_tracking/test.py:160-183), over csrc/tracking.hip.
 
     Tracker           up to 64 sequences (segments) stepped together in ONE launch; the track lists stay on the device
+    StaticTracker     the same step on the padded, device-counted StaticDetections of CenterHead.predict_static, read where they lie: every
+                      buffer allocated once, time lag and buffer parity formed on the device, one launch that a HIP graph can hold (alone
+                      or behind StaticPredictPlan.run); pack_padded + step_host is its host definition
     step_host         the numpy restatement on arrays with the same state layout: the definition the tests use, the path of CPU tensors
                       and of S2D_TRACK_DEVICE=0
     PubTracker        the reference's class on lists of dictionaries (both constructor signatures), over the same association
@@ -25,7 +28,8 @@ a read: a segment's tracks never exceed the rows of its last max_age + 1 frames 
 concatenation per field when the detections arrive as per-sample dictionaries; one upload (segment table and row offsets), no host read.
 
 Out of scope: Hungarian assignment (the reference's branch names an undefined function), any state beyond the reference's, the nuScenes
-JSON / Waymo .bin writers and the metric programs, HIP-graph capture of the step."""
+JSON / Waymo .bin writers and the metric programs, HIP-graph capture of `Tracker.step` (its parity is a host integer; `StaticTracker.run`
+is the capturable step)."""
 import os
 
 import numpy as np
@@ -35,6 +39,7 @@ from . import _lib
 
 MAX_SEGMENTS, MAX_DETS, MAX_TRACKS = 64, 1024, 4096   # S2D_TRACK_MAX_SEGMENTS / _DETS / _TRACKS
 STEP_LAUNCHES, STEP_HOST_READS, STEP_UPLOADS = 1, 0, 1
+STATIC_STEP_LAUNCHES, STATIC_STEP_HOST_READS, STATIC_STEP_UPLOADS = 1, 0, 1   # the upload is set_frames' frame block, outside the capture
 
 NUSCENES_TRACKING_NAMES = ["bicycle", "bus", "car", "motorcycle", "pedestrian", "trailer", "truck"]
 NUSCENE_CLS_VELOCITY_ERROR = {"car": 4, "truck": 4, "bus": 5.5, "trailer": 3, "pedestrian": 1, "motorcycle": 13, "bicycle": 3}
@@ -43,6 +48,8 @@ WAYMO_TRACKING_NAMES = ["VEHICLE", "PEDESTRIAN", "CYCLIST"]
 _SEGMENT = np.dtype([("pose", np.float64, (12,)), ("time_lag", np.float64), ("first", np.int32), ("skip", np.int32), ("row_lo", np.int32),
                      ("row_hi", np.int32)])   # s2d_track_segment
 assert _SEGMENT.itemsize == 120
+_FRAME = np.dtype([("pose", np.float64, (12,)), ("stamp", np.float64), ("first", np.int32), ("skip", np.int32)])   # s2d_track_frame
+assert _FRAME.itemsize == 112
 
 
 # ---- tables and state ----------------------------------------------------------------------------------------------------------------
@@ -400,6 +407,173 @@ class Tracker:
         else:
             count, id_count = (int(v) for v in head[segment])
             ct, tracking, meta = ct[segment, :count].copy(), tracking[segment, :count].copy(), meta[segment, :count].copy()
+        return dict(ids=meta[:, 1], classes=meta[:, 0], ages=meta[:, 2], active=meta[:, 3], ct=ct, tracking=tracking, id_count=id_count)
+
+
+# ---- the static device tracker: padded rows, device counts, device parity; one launch, capturable ---------------------------------------
+def pack_padded(boxes, labels, scores, counts):
+    """padded rows (boxes [S, cap, 9], labels [S, cap], scores [S, cap], counts [S]) as the packed rows of `step_host`:
+    (boxes [R, 9], labels [R], scores [R], offsets [S + 1]) with the first clamp(counts[s], 0, cap) rows of every segment.  numpy only:
+    the host definition of the static step is step_host on these rows."""
+    boxes, labels, scores = _np(boxes, np.float32), _np(labels, np.int64), _np(scores, np.float32)
+    if boxes.ndim != 3:
+        raise ValueError(f"boxes {boxes.shape}: [S, cap, 9] expected")
+    _check_boxes(boxes.shape[1:])
+    segments, cap = boxes.shape[:2]
+    counts = np.clip(_np(counts, np.int64).reshape(-1), 0, cap)
+    if labels.shape != (segments, cap) or scores.shape != (segments, cap) or counts.shape[0] != segments:
+        raise ValueError("labels and scores [S, cap] and counts [S] expected beside boxes [S, cap, 9]")
+    keep = np.arange(cap)[None, :] < counts[:, None]
+    return boxes[keep], labels[keep], scores[keep], np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+class StaticTracks:
+    """Padded results of `StaticTracker.run`, on the device and owned by the tracker (the next run overwrites them): tracking_id, active
+    int32 [S, cap]; -1 / 0 for filtered rows, for the rows at or behind the sample's count and for every row of a skipped sample."""
+    __slots__ = ("tracking_id", "active")
+
+    def __init__(self, tracking_id, active):
+        self.tracking_id, self.active = tracking_id, active
+
+    def __iter__(self):
+        return iter((self.tracking_id, self.active))
+
+    def as_list(self, det, metadata=None):
+        """`predict`'s dictionaries (box3d_lidar, scores, label_preds, metadata) of the detections `det` (a StaticDetections, or (boxes,
+        labels, scores, counts)) with tracking_id and active per sample: views into the padded buffers.  The ONE host read: the counts."""
+        boxes, labels, scores, counts = _static_inputs(det)
+        return [dict(box3d_lidar=boxes[b, :n], scores=scores[b, :n], label_preds=labels[b, :n], metadata=metadata[b] if metadata else None,
+                     tracking_id=self.tracking_id[b, :n], active=self.active[b, :n]) for b, n in enumerate(counts.tolist())]
+
+
+def _static_inputs(det):
+    if isinstance(det, tuple):
+        if len(det) != 4:
+            raise TypeError("det: a StaticDetections, or (boxes, labels, scores, counts)")
+        return det
+    return det.boxes, det.labels, det.scores, det.counts
+
+
+class StaticTracker:
+    """`samples` sequences tracked side by side on the padded, device-resident results of `CenterHead.predict_static` (StaticDetections):
+    boxes [samples, cap, 9], labels, scores [samples, cap] and counts [samples] are read where they lie.  Every buffer is allocated here,
+    once; `run` is one launch of s2d_track_step_static on the current stream with no host read, no allocation and no torch operator, and
+    the parity of the doubled state is kept on the device, so `run` can be captured into a HIP graph (alone, or behind
+    StaticPredictPlan.run) and replayed: each replay is the next step.  `set_frames` puts the poses, stamps and flags of the next run into
+    the frame block with one host-to-device copy, outside the capture.  The association is `Tracker`'s: the same device code.
+    cap * (max_age + 1) <= 4096 is the static form of Tracker's bound on a segment's tracks."""
+
+    def __init__(self, samples, cap, class_table, max_age, score_thresh=None, device=None, hungarian=False):
+        if hungarian:
+            raise NotImplementedError("StaticTracker: hungarian=True: the reference's branch calls linear_assignment, which it never defines")
+        if not 1 <= samples <= MAX_SEGMENTS:
+            raise _lib.S2DError(f"StaticTracker: {samples} samples: 1..{MAX_SEGMENTS}")
+        if not 1 <= cap <= MAX_DETS:
+            raise _lib.S2DError(f"StaticTracker: cap {cap}: 1..{MAX_DETS} rows per sample")
+        if max_age < 0:
+            raise ValueError("max_age >= 0 expected")
+        if cap * (max_age + 1) > MAX_TRACKS:
+            raise _lib.S2DError(f"StaticTracker: cap {cap} x (max_age {max_age} + 1) = {cap * (max_age + 1)} tracks: at most {MAX_TRACKS} per sample")
+        self.samples, self.cap, self.max_age = int(samples), int(cap), int(max_age)
+        self.score_thresh = None if score_thresh is None else float(score_thresh)
+        self.class_table = [(int(c), float(d)) for c, d in class_table]
+        cls_of, diff_of = _table_arrays(self.class_table)
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda":
+            raise _lib.S2DError("StaticTracker: a CUDA device expected (no CPU fallback; Tracker has the host path)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        _lib.load()
+        table = np.zeros((len(cls_of), 2), np.int32)
+        table[:, 0], table[:, 1] = cls_of, diff_of.view(np.int32)
+        self._table = torch.from_numpy(table).to(device)
+        z = lambda *shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+        s = self.samples
+        self._ct, self._tracking = z(2, s, MAX_TRACKS, 2, dtype=torch.float64), z(2, s, MAX_TRACKS, 2, dtype=torch.float64)
+        self._meta, self._head = z(2, s, MAX_TRACKS, 4, dtype=torch.int32), z(2, s, 2, dtype=torch.int32)
+        self._parity, self._prev_stamp = z(s, dtype=torch.int32), z(s, dtype=torch.float64)
+        self.frames = z(s, _FRAME.itemsize, dtype=torch.uint8)   # s2d_track_frame [samples]; set_frames fills it, or the caller does
+        self.out = StaticTracks(z(s, self.cap, dtype=torch.int32), z(s, self.cap, dtype=torch.int32))
+        self.out.tracking_id.fill_(-1)
+        self._started = np.zeros(s, np.bool_)
+
+    @classmethod
+    def waymo(cls, max_dist, cap, max_age=3, score_thresh=0.75, samples=1, device=None):
+        """labels 0 VEHICLE, 1 PEDESTRIAN, 2 CYCLIST; max_dist: name -> metres (as Tracker.waymo)"""
+        return cls(samples, cap, class_table_of(WAYMO_TRACKING_NAMES, WAYMO_TRACKING_NAMES, max_dist), max_age, score_thresh, device)
+
+    @classmethod
+    def nuscenes(cls, cap, max_age=3, samples=1, device=None, hungarian=False):
+        """labels in the class order of waymo_configs.NUSC_TASKS (as Tracker.nuscenes)"""
+        from .waymo_configs import NUSC_TASKS
+        names = [n for t in NUSC_TASKS for n in t["class_names"]]
+        return cls(samples, cap, class_table_of(names, NUSCENES_TRACKING_NAMES, NUSCENE_CLS_VELOCITY_ERROR), max_age, None, device, hungarian)
+
+    def set_frames(self, poses, stamps, first=None, skip=None):
+        """the frame block of the NEXT run, from host values: poses [S, 4, 4] float64 lidar-to-global, stamps [S] in seconds, first / skip
+        [S] (first defaults to "the sample has not been stepped yet").  One host-to-device copy on the current stream; call it once per
+        run, outside any capture."""
+        s = self.samples
+        poses = _poses(poses, s)
+        stamps = np.asarray(stamps, np.float64).reshape(-1)
+        if stamps.shape[0] != s:
+            raise ValueError(f"{stamps.shape[0]} timestamps for {s} samples")
+        skip = _flags(skip, s, False)
+        first = _flags(first, s, False) if first is not None else ~self._started & ~skip
+        if np.any(~first & ~skip & ~self._started):
+            raise ValueError("a sample's first step must have first=True (the reference's reset())")
+        block = np.zeros(s, _FRAME)
+        block["pose"], block["stamp"], block["first"], block["skip"] = poses.reshape(s, 12), stamps, first, skip
+        self.frames.copy_(torch.from_numpy(block.view(np.uint8).reshape(s, _FRAME.itemsize)))   # the step's one upload
+        self._started |= ~skip
+
+    def _check(self, det):
+        boxes, labels, scores, counts = _static_inputs(det)
+        if boxes.dim() != 3:
+            raise ValueError(f"boxes {tuple(boxes.shape)}: [{self.samples}, {self.cap}, 9] expected")
+        _check_boxes(boxes.shape[1:])
+        if tuple(boxes.shape) != (self.samples, self.cap, 9):
+            raise _lib.S2DError(f"StaticTracker.run: boxes {tuple(boxes.shape)}, the tracker was built for {(self.samples, self.cap, 9)} "
+                                "(samples, cap of the plan, 9)")
+        for name, t, dtype, shape in (("boxes", boxes, torch.float32, boxes.shape), ("labels", labels, torch.int64, (self.samples, self.cap)),
+                                      ("scores", scores, torch.float32, (self.samples, self.cap)), ("counts", counts, torch.int32, (self.samples,))):
+            if t.device != self.device or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+                raise _lib.S2DError(f"StaticTracker.run: {name} is {t.dtype} {tuple(t.shape)} on {t.device}"
+                                    f"{'' if t.is_contiguous() else ', not contiguous'}: contiguous {dtype} {tuple(shape)} on {self.device} expected "
+                                    "(the static step neither copies nor converts)")
+        return boxes, labels, scores, counts
+
+    def run(self, det):
+        """det: the StaticDetections of a plan with this tracker's samples and cap, or (boxes, labels, scores, counts) device tensors.
+        One launch on the current stream; returns the tracker's `StaticTracks` (the same tensors at every call)."""
+        boxes, labels, scores, counts = self._check(det)   # host only
+        ptr = lambda t: t.data_ptr()
+        _lib.check(_lib.load().s2d_track_step_static(ptr(boxes), ptr(labels), ptr(scores), ptr(counts), self.samples, self.cap, ptr(self.frames),
+                                                     ptr(self._table), self._table.shape[0], self.max_age,
+                                                     -1.0 if self.score_thresh is None else self.score_thresh, ptr(self._ct), ptr(self._tracking),
+                                                     ptr(self._meta), ptr(self._head), ptr(self._parity), ptr(self._prev_stamp),
+                                                     ptr(self.out.tracking_id), ptr(self.out.active), _stream(self.device)), "s2d_track_step_static")
+        return self.out
+
+    # -- results
+    def all_buffers(self):
+        """every device buffer of the tracker by name (none is ever reallocated)"""
+        return dict(table=self._table, ct=self._ct, tracking=self._tracking, meta=self._meta, head=self._head, parity=self._parity,
+                    prev_stamp=self._prev_stamp, frames=self.frames, tracking_id=self.out.tracking_id, active=self.out.active)
+
+    def buffers(self):
+        """the current state (ct, tracking, meta, head), [S, ...] each, as on Tracker: every sample's current half (the one its parity
+        names) gathered into new tensors.  Torch operators and allocations: for tests and result writers, not for the step."""
+        at = (self._parity.to(torch.int64), torch.arange(self.samples, device=self.device))
+        return self._ct[at], self._tracking[at], self._meta[at], self._head[at]
+
+    def state(self, segment):
+        """one sample's track list on the host, as Tracker.state (a copy; for tests and for writing results)"""
+        half = int(self._parity[segment].item())
+        count, id_count = self._head[half, segment].tolist()
+        ct, tracking = self._ct[half, segment, :count].cpu().numpy(), self._tracking[half, segment, :count].cpu().numpy()
+        meta = self._meta[half, segment, :count].cpu().numpy()
         return dict(ids=meta[:, 1], classes=meta[:, 0], ages=meta[:, 2], active=meta[:, 3], ct=ct, tracking=tracking, id_count=id_count)
 
 
