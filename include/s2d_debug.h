@@ -36,6 +36,22 @@ int s2d_conv2d_debug_force(int bm, int ns, int shared_a, int conv1x1_k64);
  * the geometry is valid) for shapes or epilogues the entry refuses.  No device work. */
 int s2d_conv2d_plan(int kind, int n, int h, int w, int cin, int cout, int pad, int stride, int ks, int32_t out[8]);
 
+/* test / tuning aids of the dense 2-D weight-gradient kernels (csrc/conv2d_wgrad.hip; tests/test_conv2d_wgrad_parity_gpu.py sweeps every
+ * instantiation and K-loop length in one process with them).  ring_deep = 0 / 1: the four-slot LDS ring / as many slots as fit (what
+ * S2D_WG_RING_DEEP, read from the environment at first use, selects); splits >= 1 replaces the term CUs / (grid y * channel tiles) of the
+ * split count before its clamps (at most one split per K-step; the count is then re-derived from the rounded-up steps per workgroup);
+ * -1 = as the environment / the CU count says.  Overrides all launches AND *_wgrad_workspace_bytes queries that follow (the Python
+ * package memoises those queries: force only around raw-pointer calls, and restore with (-1, -1)).  Any other value: S2D_ERR_INVALID_ARG,
+ * nothing changed. */
+int s2d_conv2d_wgrad_debug_force(int ring_deep, int splits);
+
+/* the launch plan a weight-gradient entry takes for these arguments - the function the launchers and the three *_wgrad_workspace_bytes
+ * queries read.  kind: 0 conv2d3x3_wgrad (ks 3), 1 conv2d1x1_wgrad (ks 1, pad 0), 2 conv2d_s2_wgrad (ks 3 or 4, pad 1); (n, h, w) as the
+ * entry takes them; c_in_role = channels of the tensor the taps walk over (cin; cb of the stride-2 entry), c_out_role = of the other
+ * (cout; ca).  out = {TCO, TCI, NS (LDS ring slots), KXN (kx taps per workgroup), splits, K-steps per workgroup, grid y, grid z}.
+ * Returns S2D_ERR_UNSUPPORTED for shapes the entry refuses.  No device work. */
+int s2d_conv2d_wgrad_plan(int kind, int n, int h, int w, int c_in_role, int c_out_role, int pad, int ks, int32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

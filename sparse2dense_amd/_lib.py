@@ -320,6 +320,9 @@ SIGNATURES = {
     # include/s2d_debug.h: plan override and plan report of the dense 2-D tile kernels (tests/test_conv2d_parity_gpu.py)
     "s2d_conv2d_debug_force": (ctypes.c_int, [ctypes.c_int] * 4),
     "s2d_conv2d_plan": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int32)]),
+    # ... and of the dense 2-D weight-gradient kernels (tests/test_conv2d_wgrad_parity_gpu.py)
+    "s2d_conv2d_wgrad_debug_force": (ctypes.c_int, [ctypes.c_int] * 2),
+    "s2d_conv2d_wgrad_plan": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int32)]),
     "s2d_conv2d1x1_bnbwd_supported": (ctypes.c_int, [ctypes.c_int] * 2),
     "s2d_conv2d1x1_nhwc_bf16_bnbwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p,
                                                                                                     ctypes.c_int, c_f32p, ctypes.c_void_p]),

@@ -361,15 +361,48 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float4 
     }
 }
 
+// ---- launch plan --------------------------------------------------------------------------------------------------
+// One function (wg_plan) decides channel tiles, ring depth, split count and grid of every entry below; the launchers, the three
+// *_workspace_bytes queries and the report s2d_conv2d_wgrad_plan (include/s2d_debug.h) all read it, so what is reported is what is
+// launched.  S2D_WG_RING_DEEP is read from the environment at first use into a file-level value that s2d_conv2d_wgrad_debug_force can
+// override afterwards, together with the split count (tests sweep every instantiation and K-loop length in one process).
+enum { WG_K3 = 0, WG_K1 = 1, WG_S2 = 2 };   // `kind` of the plan: 3x3 stride 1, 1x1, stride 2 (ks 3 or 4)
 struct WgPlan {
-    int tco, tci, splits, steps_per_block;
+    int tco, tci, ns, kxn, splits, steps_per_block, grid_y, grid_z;
+    bool deep;
     size_t ws_bytes;
 };
 static bool wg_supported(int cin, int cout) { return cin % 64 == 0 && cout % 64 == 0 && cin >= 64 && cout >= 64; }
-static WgPlan wg_plan(int n_img, int h, int w, int cin, int cout, int pad, int ks = 3, int stride = 1, int kxg = 1) {
+
+static int g_wg_deep = 1;       // 0: the four-slot ring everywhere (S2D_WG_RING_DEEP=0, the r01-r05 kernel)
+static int g_wg_splits = -1;    // >= 1: replaces the CU-count term of the split count (before its clamps)
+static int wg_env_deep() { const char *e = getenv("S2D_WG_RING_DEEP"); return e ? (atoi(e) != 0) : 1; }
+static void wg_switches_init() {
+    static const bool once = [] {
+        g_wg_deep = wg_env_deep();
+        return true;
+    }();
+    (void)once;
+}
+
+// ring depth of each instantiation, from WgCfg itself, indexed the way the launchers dispatch: [variant][TCO 128][TCI 128][DEEP]
+#define S2D_WG_NS_ROW(KS_, ST_, TCO_, TCI_) {WgCfg<TCO_, TCI_, KS_, ST_, false>::NS, WgCfg<TCO_, TCI_, KS_, ST_, true>::NS}
+#define S2D_WG_NS_VARIANT(KS_, ST_) {{S2D_WG_NS_ROW(KS_, ST_, 64, 64), S2D_WG_NS_ROW(KS_, ST_, 64, 128)}, {S2D_WG_NS_ROW(KS_, ST_, 128, 64), S2D_WG_NS_ROW(KS_, ST_, 128, 128)}}
+static constexpr int WG_NS[4][2][2][2] = {S2D_WG_NS_VARIANT(3, 1), S2D_WG_NS_VARIANT(1, 1), S2D_WG_NS_VARIANT(3, 2), S2D_WG_NS_VARIANT(4, 2)};
+#undef S2D_WG_NS_VARIANT
+#undef S2D_WG_NS_ROW
+
+// cin / cout are the kernel's roles: cin = channels of the tensor the taps walk over (x; b of the stride-2 entry), cout = of the other
+static WgPlan wg_plan(int kind, int n_img, int h, int w, int cin, int cout, int pad, int ks) {
+    wg_switches_init();
+    const int stride = kind == WG_S2 ? 2 : 1;
     WgPlan p;
+    p.kxn = ks == 4 ? 2 : ks;
+    const int kxg = ks / p.kxn;
     p.tco = cout % 128 == 0 ? 128 : 64;
     p.tci = cin % 128 == 0 ? 128 : 64;
+    p.deep = g_wg_deep != 0;
+    p.ns = WG_NS[kind == WG_S2 ? (ks == 4 ? 3 : 2) : kind][p.tco == 128][p.tci == 128][p.deep];
     const int ho = (h + 2 * pad - ks) / stride + 1, wo = (w + 2 * pad - ks) / stride + 1;
     const int64_t total = (int64_t)n_img * ho * ((wo + 31) / 32);
     const int tiles = (cout / p.tco) * (cin / p.tci);
@@ -382,23 +415,22 @@ static WgPlan wg_plan(int n_img, int h, int w, int cin, int cout, int pad, int k
             n = 256;
         cus = n;
     }
-    int64_t splits = cus / (ks * kxg * tiles);
+    int64_t splits = g_wg_splits >= 1 ? g_wg_splits : cus / (ks * kxg * tiles);
     if (splits > total) splits = total;
     if (splits < 1) splits = 1;
     p.steps_per_block = (int)ceil_div(total, splits);
     p.splits = (int)ceil_div(total, p.steps_per_block);
+    p.grid_y = ks * kxg;
+    p.grid_z = tiles;
     p.ws_bytes = (size_t)p.splits * ks * ks * cout * cin * sizeof(float) + (size_t)p.splits * cout * sizeof(float);   // + bias-gradient rows
     return p;
 }
-
-// S2D_WG_RING_DEEP=0: the four-slot ring everywhere (the r01-r05 kernel)
-static bool wg_ring_deep() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("S2D_WG_RING_DEEP");
-        v = e ? (atoi(e) != 0) : 1;
-    }
-    return v != 0;
+// the shapes each entry accepts (its own argument checks say why it refuses one)
+static bool wg_shape_ok(int kind, int n_img, int h, int w, int cin, int cout, int pad, int ks) {
+    if (!wg_supported(cin, cout) || n_img <= 0 || h <= 0 || w <= 0) return false;
+    if (kind == WG_K3) return ks == 3 && (pad == 0 || pad == 1) && h + 2 * pad - 2 > 0 && w + 2 * pad - 2 > 0;
+    if (kind == WG_K1) return ks == 1 && pad == 0;
+    return kind == WG_S2 && (ks == 3 || ks == 4) && pad == 1 && h % 2 == 0 && w % 2 == 0;
 }
 
 template <int TCO, int TCI, int KS = 3, int STRIDE = 1, int KXN = KS, bool DEEP = false>
@@ -411,7 +443,7 @@ static int wg_launch_ring(const WgPlan &p, const __bf16 *x, const __bf16 *dy, co
         S2D_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS));
         attr_set = true;
     }
-    const dim3 grid(p.splits, KS * (KS / KXN), (cout / TCO) * (cin / TCI));
+    const dim3 grid(p.splits, p.grid_y, p.grid_z);
     hipLaunchKernelGGL(kern, grid, dim3(512), C::LDS, st, x, dy, zero_page, n_img, h, w, cin, cout, pad, p.steps_per_block, partial,
                        dbias_partial);
     S2D_LAUNCH_CHECK();
@@ -421,7 +453,7 @@ static int wg_launch_ring(const WgPlan &p, const __bf16 *x, const __bf16 *dy, co
 template <int TCO, int TCI, int KS = 3, int STRIDE = 1, int KXN = KS>
 static int wg_launch(const WgPlan &p, const __bf16 *x, const __bf16 *dy, const __bf16 *zero_page, int n_img, int h, int w, int cin,
                      int cout, int pad, float *partial, hipStream_t st, float *dbias_partial = nullptr) {
-    if (wg_ring_deep())
+    if (p.deep)
         return wg_launch_ring<TCO, TCI, KS, STRIDE, KXN, true>(p, x, dy, zero_page, n_img, h, w, cin, cout, pad, partial, st, dbias_partial);
     return wg_launch_ring<TCO, TCI, KS, STRIDE, KXN, false>(p, x, dy, zero_page, n_img, h, w, cin, cout, pad, partial, st, dbias_partial);
 }
@@ -432,9 +464,33 @@ using namespace s2d;
 
 extern "C" int s2d_conv2d3x3_wgrad_supported(int cin, int cout) { return wg_supported(cin, cout); }
 
+/* include/s2d_debug.h */
+extern "C" int s2d_conv2d_wgrad_debug_force(int ring_deep, int splits) {
+    S2D_CHECK_ARG(ring_deep >= -1 && ring_deep <= 1 && (splits == -1 || (splits >= 1 && splits <= 65535)),
+                  "conv2d_wgrad_debug_force: ring_deep -1/0/1, splits -1 or 1..65535");
+    wg_switches_init();
+    g_wg_deep = ring_deep == -1 ? wg_env_deep() : ring_deep;
+    g_wg_splits = splits;
+    return S2D_OK;
+}
+
+/* include/s2d_debug.h.  out = {TCO, TCI, NS, KXN, splits, steps per block, grid y, grid z} */
+extern "C" int s2d_conv2d_wgrad_plan(int kind, int n, int h, int w, int c_in_role, int c_out_role, int pad, int ks, int32_t out[8]) {
+    S2D_CHECK_ARG(out, "conv2d_wgrad_plan: null argument");
+    if (!wg_shape_ok(kind, n, h, w, c_in_role, c_out_role, pad, ks)) {
+        set_error("conv2d_wgrad_plan: kind %d is not supported for %d x %d x %d, channels %d (taps) x %d, pad %d, ks %d", kind, n, h, w, c_in_role,
+                  c_out_role, pad, ks);
+        return S2D_ERR_UNSUPPORTED;
+    }
+    const WgPlan p = wg_plan(kind, n, h, w, c_in_role, c_out_role, pad, ks);
+    const int v[8] = {p.tco, p.tci, p.ns, p.kxn, p.splits, p.steps_per_block, p.grid_y, p.grid_z};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return S2D_OK;
+}
+
 extern "C" size_t s2d_conv2d3x3_wgrad_workspace_bytes(int n_img, int h, int w, int cin, int cout, int pad) {
-    if (!wg_supported(cin, cout) || n_img <= 0 || h + 2 * pad - 2 <= 0 || w + 2 * pad - 2 <= 0) return 0;
-    return wg_plan(n_img, h, w, cin, cout, pad).ws_bytes;
+    if (!wg_shape_ok(WG_K3, n_img, h, w, cin, cout, pad, 3)) return 0;
+    return wg_plan(WG_K3, n_img, h, w, cin, cout, pad, 3).ws_bytes;
 }
 
 extern "C" int s2d_conv2d3x3_wgrad_nhwc_bf16(const void *x, const void *dy, const void *zero_page, int n_img, int h, int w, int cin,
@@ -445,7 +501,7 @@ extern "C" int s2d_conv2d3x3_wgrad_nhwc_bf16(const void *x, const void *dy, cons
         return S2D_ERR_UNSUPPORTED;
     }
     S2D_CHECK_ARG(h + 2 * pad - 2 > 0 && w + 2 * pad - 2 > 0, "conv2d3x3_wgrad: empty output");
-    const WgPlan p = wg_plan(n_img, h, w, cin, cout, pad);
+    const WgPlan p = wg_plan(WG_K3, n_img, h, w, cin, cout, pad, 3);
     if (!ws || ws_bytes < p.ws_bytes) {
         set_error("conv2d3x3_wgrad: workspace too small (%zu < %zu)", ws_bytes, p.ws_bytes);
         return S2D_ERR_WORKSPACE;
@@ -470,8 +526,8 @@ extern "C" int s2d_conv2d3x3_wgrad_nhwc_bf16(const void *x, const void *dy, cons
 
 /* 1x1 convolution (stride 1): dW[co][ci] = sum over pixels of dY[m][co] * X[m][ci], same kernel with one tap */
 extern "C" size_t s2d_conv2d1x1_wgrad_workspace_bytes(int n_img, int h, int w, int cin, int cout) {
-    if (!wg_supported(cin, cout) || n_img <= 0 || h <= 0 || w <= 0) return 0;
-    return wg_plan(n_img, h, w, cin, cout, 0, 1).ws_bytes;
+    if (!wg_shape_ok(WG_K1, n_img, h, w, cin, cout, 0, 1)) return 0;
+    return wg_plan(WG_K1, n_img, h, w, cin, cout, 0, 1).ws_bytes;
 }
 
 extern "C" int s2d_conv2d1x1_wgrad_nhwc_bf16(const void *x, const void *dy, const void *zero_page, int n_img, int h, int w, int cin, int cout,
@@ -481,7 +537,7 @@ extern "C" int s2d_conv2d1x1_wgrad_nhwc_bf16(const void *x, const void *dy, cons
         set_error("conv2d1x1_wgrad: unsupported channels %d -> %d", cin, cout);
         return S2D_ERR_UNSUPPORTED;
     }
-    const WgPlan p = wg_plan(n_img, h, w, cin, cout, 0, 1);
+    const WgPlan p = wg_plan(WG_K1, n_img, h, w, cin, cout, 0, 1);
     if (!ws || ws_bytes < p.ws_bytes) {
         set_error("conv2d1x1_wgrad: workspace too small (%zu < %zu)", ws_bytes, p.ws_bytes);
         return S2D_ERR_WORKSPACE;
@@ -510,8 +566,8 @@ extern "C" int s2d_conv2d1x1_wgrad_nhwc_bf16(const void *x, const void *dy, cons
 extern "C" int s2d_conv2d_s2_wgrad_supported(int ca, int cb, int ks) { return wg_supported(cb, ca) && (ks == 3 || ks == 4); }
 
 extern "C" size_t s2d_conv2d_s2_wgrad_workspace_bytes(int n_img, int h, int w, int ca, int cb, int ks) {
-    if (!s2d_conv2d_s2_wgrad_supported(ca, cb, ks) || n_img <= 0 || h < 2 || w < 2 || h % 2 || w % 2) return 0;
-    return wg_plan(n_img, h, w, cb, ca, 1, ks, 2, ks == 4 ? 2 : 1).ws_bytes;
+    if (!wg_shape_ok(WG_S2, n_img, h, w, cb, ca, 1, ks)) return 0;
+    return wg_plan(WG_S2, n_img, h, w, cb, ca, 1, ks).ws_bytes;
 }
 
 extern "C" int s2d_conv2d_s2_wgrad_nhwc_bf16(const void *a, const void *b, const void *zero_page, int n_img, int h, int w, int ca, int cb,
@@ -521,7 +577,7 @@ extern "C" int s2d_conv2d_s2_wgrad_nhwc_bf16(const void *a, const void *b, const
         set_error("conv2d_s2_wgrad: unsupported channels %d x %d, kernel %d", ca, cb, ks);
         return S2D_ERR_UNSUPPORTED;
     }
-    const WgPlan p = wg_plan(n_img, h, w, cb, ca, 1, ks, 2, ks == 4 ? 2 : 1);
+    const WgPlan p = wg_plan(WG_S2, n_img, h, w, cb, ca, 1, ks);
     if (!ws || ws_bytes < p.ws_bytes) {
         set_error("conv2d_s2_wgrad: workspace too small (%zu < %zu)", ws_bytes, p.ws_bytes);
         return S2D_ERR_WORKSPACE;

@@ -108,6 +108,50 @@ def test_default_conv2d_plans_are_the_pinned_ones(lib):
             assert tuple(C.mirror_plan(shapes[i], 256)) == want, (shapes[i], C.mirror_plan(shapes[i], 256))
 
 
+def test_default_conv2d_wgrad_plans_are_the_pinned_ones(lib):
+    """With nothing forced, the plan report s2d_conv2d_wgrad_plan (the function the launchers and the three *_wgrad_workspace_bytes queries
+    read) equals the launch arithmetic of the commit before the override entries existed, restated in tests/conv2d_wgrad_ref.mirror_plan
+    (tiles of 128 where the channels allow, splits = CUs / (grid y * tiles) rounded down, clamped, re-derived from the rounded-up steps
+    per workgroup; the deep ring), for the benchmark's 3x3, 1x1, 3x3 stride-2 and 4x4 stride-2 layer shapes.  No launch."""
+    import ctypes
+    import torch
+    import conv2d_wgrad_ref as W
+    assert os.environ.get("S2D_WG_RING_DEEP") is None, "S2D_WG_RING_DEEP is set: the library would not take its default plan"
+    cus = torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+    assert lib.s2d_conv2d_wgrad_debug_force(-1, -1) == 0
+    shapes = [W.geo(W.K3, 4, 188, 188, 128, 128, 1), W.geo(W.K3, 4, 94, 94, 256, 256, 1), W.geo(W.K3, 4, 188, 188, 512, 64, 1),
+              W.geo(W.K3, 4, 188, 188, 64, 64, 1), W.geo(W.K3, 4, 188, 188, 256, 128, 1), W.geo(W.K3, 1, 188, 188, 128, 128, 1),
+              W.geo(W.K1, 4, 188, 188, 256, 256), W.geo(W.K1, 4, 47, 47, 1024, 256), W.geo(W.K1, 4, 47, 47, 256, 1024), W.geo(W.K1, 4, 188, 188, 64, 64),
+              W.geo(W.S2, 4, 188, 188, 128, 256, ks=3), W.geo(W.S2, 4, 376, 376, 64, 128, ks=3),
+              W.geo(W.S2, 4, 94, 94, 256, 256, ks=4), W.geo(W.S2, 4, 188, 188, 256, 256, ks=4), W.geo(W.S2, 4, 116, 116, 64, 64, ks=4)]
+    out = (ctypes.c_int32 * 8)()
+    queries = {W.K3: lambda g: lib.s2d_conv2d3x3_wgrad_workspace_bytes.__wrapped__(g.n, g.h, g.w, g.cin, g.cout, g.pad),
+               W.K1: lambda g: lib.s2d_conv2d1x1_wgrad_workspace_bytes.__wrapped__(g.n, g.h, g.w, g.cin, g.cout),
+               W.S2: lambda g: lib.s2d_conv2d_s2_wgrad_workspace_bytes.__wrapped__(g.n, g.h, g.w, g.cout, g.cin, g.ks)}
+    for g in shapes:
+        assert lib.s2d_conv2d_wgrad_plan(g.kind, g.n, g.h, g.w, g.cin, g.cout, g.pad, g.ks, out) == 0, (g, _lib.last_error())
+        plan = W.Plan(*list(out))
+        assert plan == W.mirror_plan(g, cus), g
+        assert plan.splits * plan.gy * plan.gz <= cus                      # never more workgroups than CUs
+        assert queries[g.kind](g) == 4 * W.ws_floats(g, plan), g
+    if cus == 256:   # the values themselves: 4512 K-steps on 85 -> 84 splits of 54; on 64 splits of 71; 376 on 8 splits of 47 (NS 5)
+        pinned = {0: (128, 128, 8, 3, 84, 54, 3, 1), 6: (128, 128, 8, 1, 64, 71, 1, 4), 12: (128, 128, 5, 2, 8, 47, 8, 4)}
+        for i, want in pinned.items():
+            assert tuple(W.mirror_plan(shapes[i], 256)) == want, (shapes[i], W.mirror_plan(shapes[i], 256))
+    # refused shapes: the report says so, the queries answer 0, a bad override changes nothing
+    assert lib.s2d_conv2d_wgrad_plan(W.K3, 4, 188, 188, 100, 128, 1, 3, out) == -2 and lib.s2d_conv2d_wgrad_plan(W.S2, 4, 187, 188, 64, 64, 1, 3, out) == -2
+    assert lib.s2d_conv2d_wgrad_debug_force(2, -1) == -1 and lib.s2d_conv2d_wgrad_debug_force(-1, 0) == -1
+    assert lib.s2d_conv2d_wgrad_plan(W.K3, 4, 188, 188, 128, 128, 1, 3, out) == 0 and tuple(out) == tuple(W.mirror_plan(shapes[0], cus))
+    try:   # the override reaches the report and the queries alike
+        assert lib.s2d_conv2d_wgrad_debug_force(0, 7) == 0
+        g = shapes[0]
+        assert lib.s2d_conv2d_wgrad_plan(g.kind, g.n, g.h, g.w, g.cin, g.cout, g.pad, g.ks, out) == 0
+        assert W.Plan(*list(out)) == W.mirror_plan(g, cus, deep=False, splits=7) and out[2] == 4 and out[4] == 7
+        assert queries[g.kind](g) == 4 * W.ws_floats(g, W.Plan(*list(out)))
+    finally:
+        assert lib.s2d_conv2d_wgrad_debug_force(-1, -1) == 0
+
+
 def test_ops_fail_loudly_on_cpu_tensors():
     import torch
     from sparse2dense_amd import hip_ops
