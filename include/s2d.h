@@ -1241,6 +1241,19 @@ int s2d_deform_conv_wgrad_nhwc_bf16(const void *x, const void *offset, int offse
  * s2d_roi_refine (roi_head_template.py:153-183 generate_predicted_boxes + two_stage.py:124-150 post_process): n = B * cap RoIs;
  * boxes [n][7] = the residual rcnn_reg [n][7] plus the RoI's size and heading, rotated by its yaw and moved to its centre; scores [n] =
  * sqrt(sigmoid(rcnn_cls) * roi_score); labels [n] int64 = roi_label - 1 (-1 on the padding, which the caller slices off).
+ *
+ * The static forms read padded rows with DEVICE counts where they lie (center_predict.StaticDetections) and take no host table: launches
+ * only, capturable into a HIP graph behind the static predict (second_stage.StaticRoIPlan).
+ *
+ * s2d_roi_pack_static: boxes [B][det_cap][7] (heading last), scores [B][det_cap], labels [B][det_cap] int64, counts [B] int32, all on the
+ * device, 1 <= B <= S2D_ROI_MAX_BATCH, B * det_cap < 2^31.  With n_b = clamp(counts[b], 0, min(det_cap, cap)): slot i < n_b of sample b
+ * gets rois [B][cap][7], roi_scores [B][cap], roi_labels [B][cap] int64 = label + 1 of input row (b, i) and row [B][cap] int32 =
+ * b * det_cap + i; the slots >= n_b are all zero with label 0 and row -1 (as s2d_roi_pack pads); out_counts [B] int32 = n_b.  No input
+ * row at or behind counts[b] is read.  `row` is the table s2d_roi_bev_features takes over `boxes` as the packed list [B * det_cap][7].
+ *
+ * s2d_roi_refine_static: s2d_roi_refine (the same device function) on [B][cap] with counts [B] int32 on the device: the rows < counts[b]
+ * get its result, the rows >= counts[b] are WRITTEN as zero boxes, zero scores and label -1 and their inputs are not read - every output
+ * element is a function of the rows below the counts alone.
  */
 #define S2D_ROI_MAX_GT 512
 #define S2D_ROI_MAX_BATCH 64
@@ -1259,6 +1272,12 @@ int s2d_roi_targets(const int32_t *idx, int batch, int per, int cap, int roi_dim
                     void *rcnn_cls_labels, s2d_stream_t stream);
 int s2d_roi_refine(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *rcnn_cls, const float *rcnn_reg,
                    int64_t n, float *boxes, float *scores, int64_t *labels, s2d_stream_t stream);
+int s2d_roi_pack_static(const float *boxes, const float *scores, const int64_t *labels, const int32_t *counts, int batch, int det_cap,
+                        int cap, float *rois, float *roi_scores, int64_t *roi_labels, int32_t *row, int32_t *out_counts,
+                        s2d_stream_t stream);
+int s2d_roi_refine_static(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *rcnn_cls,
+                          const float *rcnn_reg, const int32_t *counts, int batch, int cap, float *boxes, float *scores, int64_t *labels,
+                          s2d_stream_t stream);
 
 /*
  * The eval-mode RoI MLP in one launch (csrc/roi_mlp.hip; roi_head.py:16-106, roi_head_template.py:27-41): feats [rows][cin] fp32

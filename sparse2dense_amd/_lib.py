@@ -473,6 +473,8 @@ SIGNATURES = {
     "s2d_roi_targets": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_int] +
                         [ctypes.c_double] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 9),
     "s2d_roi_refine": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    "s2d_roi_pack_static": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 6),
+    "s2d_roi_refine_static": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4),
     # the eval RoI MLP in one launch (csrc/roi_mlp.hip)
     "s2d_roi_mlp_supported": (ctypes.c_int, [ctypes.c_int] * 12),
     "s2d_roi_mlp_packed_elems": (ctypes.c_int64, [ctypes.c_int] * 12),

@@ -7,6 +7,10 @@
 //   roi_match_gt_kernel      best 3-D IoU and its ground-truth row for every RoI of every sample (bev_overlap of nms_geom.h directly)
 //   roi_targets_kernel       gather of the sampled RoIs + residual targets in the RoI's frame + reg mask + classification labels
 //   roi_refine_kernel        generate_predicted_boxes + the arithmetic of post_process
+// and the two forms that read padded rows with DEVICE counts where they lie (StaticDetections), launches only, so that predict_static +
+// second stage can be captured into one HIP graph:
+//   roi_pack_static_kernel   padded [B, det_cap] detections + counts [B] -> the [B, cap] RoI tensors, the row table and the clamped counts
+//   roi_refine_static_kernel roi_refine_kernel's arithmetic (the same device function) on the rows below counts[b], zeros / -1 behind them
 // Expression order follows the torch chain on fp32 (the library is built with -ffp-contract=off): divisions are divisions, python
 // scalars enter as their fp32 rounding.  Built without the SLP vectoriser (DESIGN rule 36): the file has fp32 blends and runs inside
 // two-stage training beside the weight-gradient stream.
@@ -20,6 +24,8 @@ namespace s2d {
 constexpr int ROI_MAX_GT = S2D_ROI_MAX_GT;
 
 constexpr int ROI_MAX_BATCH = S2D_ROI_MAX_BATCH;
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // first row of every sample in the packed lists (and the total behind the last): travels by value in the kernel arguments
 struct PackOffsets {
@@ -39,6 +45,32 @@ __global__ __launch_bounds__(256) void roi_pack_kernel(const float *__restrict__
     rois[s * 7 + 6] = valid ? bx[box_dim - 1] : 0.f;
     roi_scores[s] = valid ? scores[r] : 0.f;
     roi_labels[s] = valid ? labels[r] + 1 : 0;
+}
+
+// The padded form: sample b's detections are the first counts[b] rows of boxes [B][det_cap][7] (scores, labels [B][det_cap]); the count is
+// read on the device and clamped to what both sides hold.  Nothing at or behind the count is read: the padding may hold anything.  row is the
+// table s2d_roi_bev_features takes over the boxes viewed as [B * det_cap][7].
+__global__ __launch_bounds__(256) void roi_pack_static_kernel(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                              const int64_t *__restrict__ labels, const int32_t *__restrict__ counts,
+                                                              int det_cap, int cap, float *__restrict__ rois, float *__restrict__ roi_scores,
+                                                              int64_t *__restrict__ roi_labels, int32_t *__restrict__ row,
+                                                              int32_t *__restrict__ out_counts) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = clampi(counts[b], 0, det_cap < cap ? det_cap : cap);
+    if (i == 0) out_counts[b] = n;
+    if (i >= cap) return;
+    const int64_t s = (int64_t)b * cap + i, r = (int64_t)b * det_cap + i;
+    if (i < n) {
+        for (int e = 0; e < 7; ++e) rois[s * 7 + e] = boxes[r * 7 + e];
+        roi_scores[s] = scores[r];
+        roi_labels[s] = labels[r] + 1;
+        row[s] = (int32_t)r;
+        return;
+    }
+    for (int e = 0; e < 7; ++e) rois[s * 7 + e] = 0.f;   // (no load on this side: the padding of the inputs is never touched)
+    roi_scores[s] = 0.f;
+    roi_labels[s] = 0;
+    row[s] = -1;
 }
 
 // ---- BEV features -----------------------------------------------------------------------------------------------------------------------
@@ -65,8 +97,6 @@ __device__ __forceinline__ float widen(unsigned short v) { return __uint_as_floa
 // floor of a map coordinate as an int that is safe to clamp: NaN and anything below -2 become -2, anything above `size` becomes `size`;
 // after the clamp of x0 and x0 + 1 to [0, size - 1] that is what floor().long().clamp() gives
 __device__ __forceinline__ int cell_of(float v, int size) { return (int)fminf(fmaxf(floorf(v), -2.f), (float)size); }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the sample point `p` of box bx (two_stage.py:50-74 over box_torch_ops.center_to_corner_box2d / rotation_2d): 0 the centre, 1..4 the
 // middles of the corner pairs (0, 1), (2, 3), (0, 3), (1, 2); corners clockwise from the minimum point
@@ -316,12 +346,10 @@ __global__ __launch_bounds__(256) void roi_targets_kernel(TargetArgs a) {
 }
 
 // ---- refine -------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void roi_refine_kernel(const float *__restrict__ rois, const float *__restrict__ roi_scores,
-                                                         const int64_t *__restrict__ roi_labels, const float *__restrict__ cls,
-                                                         const float *__restrict__ reg, int64_t n, float *__restrict__ boxes,
-                                                         float *__restrict__ scores, int64_t *__restrict__ labels) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
+// RoI t of the flat [n] lists: the one statement of the arithmetic, shared by the two kernels below
+__device__ __forceinline__ void refine_row(const float *__restrict__ rois, const float *__restrict__ roi_scores,
+                                           const int64_t *__restrict__ roi_labels, const float *__restrict__ cls, const float *__restrict__ reg,
+                                           int64_t t, float *__restrict__ boxes, float *__restrict__ scores, int64_t *__restrict__ labels) {
     const float *roi = rois + t * 7, *res = reg + t * 7;
     float v[7];
     for (int e = 0; e < 3; ++e) v[e] = res[e] + 0.f;   // roi_head_template.py:166-171: the RoI's centre is zeroed before the sum
@@ -335,6 +363,34 @@ __global__ __launch_bounds__(256) void roi_refine_kernel(const float *__restrict
     for (int e = 3; e < 7; ++e) o[e] = v[e];
     scores[t] = sqrtf(1.f / (1.f + expf(-cls[t])) * roi_scores[t]);
     labels[t] = roi_labels[t] - 1;
+}
+
+__global__ __launch_bounds__(256) void roi_refine_kernel(const float *__restrict__ rois, const float *__restrict__ roi_scores,
+                                                         const int64_t *__restrict__ roi_labels, const float *__restrict__ cls,
+                                                         const float *__restrict__ reg, int64_t n, float *__restrict__ boxes,
+                                                         float *__restrict__ scores, int64_t *__restrict__ labels) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    refine_row(rois, roi_scores, roi_labels, cls, reg, t, boxes, scores, labels);
+}
+
+// [B][cap] with counts [B] on the device: the rows at and behind counts[b] are written as zeros with label -1 and their inputs are not
+// read, so every output element is a function of the rows below the counts alone (the MLP's values for the padding never arrive)
+__global__ __launch_bounds__(256) void roi_refine_static_kernel(const float *__restrict__ rois, const float *__restrict__ roi_scores,
+                                                                const int64_t *__restrict__ roi_labels, const float *__restrict__ cls,
+                                                                const float *__restrict__ reg, const int32_t *__restrict__ counts, int cap,
+                                                                float *__restrict__ boxes, float *__restrict__ scores,
+                                                                int64_t *__restrict__ labels) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= cap) return;
+    const int64_t t = (int64_t)b * cap + i;
+    if (i < counts[b]) {
+        refine_row(rois, roi_scores, roi_labels, cls, reg, t, boxes, scores, labels);
+        return;
+    }
+    for (int e = 0; e < 7; ++e) boxes[t * 7 + e] = 0.f;
+    scores[t] = 0.f;
+    labels[t] = -1;
 }
 
 }  // namespace s2d
@@ -356,6 +412,20 @@ extern "C" int s2d_roi_pack(const float *boxes, const float *scores, const int64
     S2D_CHECK_ARG(offsets[batch] == 0 || (boxes && scores && labels), "roi_pack: null box list");
     hipLaunchKernelGGL(roi_pack_kernel, dim3((unsigned)ceil_div(cap, 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels,
                        box_dim, off, cap, rois, roi_scores, roi_labels);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
+}
+
+extern "C" int s2d_roi_pack_static(const float *boxes, const float *scores, const int64_t *labels, const int32_t *counts, int batch, int det_cap,
+                                   int cap, float *rois, float *roi_scores, int64_t *roi_labels, int32_t *row, int32_t *out_counts,
+                                   s2d_stream_t stream) {
+    S2D_CHECK_ARG(batch >= 1 && batch <= ROI_MAX_BATCH, "roi_pack_static: batch %d (1..%d)", batch, ROI_MAX_BATCH);
+    S2D_CHECK_ARG(det_cap >= 1 && cap >= 1, "roi_pack_static: det_cap %d, cap %d (>= 1 each)", det_cap, cap);
+    S2D_CHECK_ARG((int64_t)batch * det_cap < (1ll << 31), "roi_pack_static: %lld detection rows (int32 row table)", (long long)batch * det_cap);
+    S2D_CHECK_ARG(boxes && scores && labels && counts, "roi_pack_static: null boxes, scores, labels or counts");
+    S2D_CHECK_ARG(rois && roi_scores && roi_labels && row && out_counts, "roi_pack_static: null output");
+    hipLaunchKernelGGL(roi_pack_static_kernel, dim3((unsigned)ceil_div(cap, 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, boxes, scores,
+                       labels, counts, det_cap, cap, rois, roi_scores, roi_labels, row, out_counts);
     S2D_LAUNCH_CHECK();
     return S2D_OK;
 }
@@ -451,6 +521,18 @@ extern "C" int s2d_roi_refine(const float *rois, const float *roi_scores, const 
     S2D_CHECK_ARG(boxes && scores && labels, "roi_refine: null output");
     hipLaunchKernelGGL(roi_refine_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, rois, roi_scores, roi_labels, rcnn_cls,
                        rcnn_reg, n, boxes, scores, labels);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
+}
+
+extern "C" int s2d_roi_refine_static(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *rcnn_cls,
+                                     const float *rcnn_reg, const int32_t *counts, int batch, int cap, float *boxes, float *scores,
+                                     int64_t *labels, s2d_stream_t stream) {
+    S2D_CHECK_ARG(batch >= 1 && batch <= 65535 && cap >= 1, "roi_refine_static: batch %d (1..65535), cap %d (>= 1)", batch, cap);
+    S2D_CHECK_ARG(rois && roi_scores && roi_labels && rcnn_cls && rcnn_reg && counts, "roi_refine_static: null input");
+    S2D_CHECK_ARG(boxes && scores && labels, "roi_refine_static: null output");
+    hipLaunchKernelGGL(roi_refine_static_kernel, dim3((unsigned)ceil_div(cap, 256), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, rois,
+                       roi_scores, roi_labels, rcnn_cls, rcnn_reg, counts, cap, boxes, scores, labels);
     S2D_LAUNCH_CHECK();
     return S2D_OK;
 }

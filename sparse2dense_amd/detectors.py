@@ -278,6 +278,15 @@ class VoxelNet(SingleStageDetector):
             return boxes, x, voxel_feature, self.bbox_head.loss(example, preds)
         return boxes, x, voxel_feature, None, F_D_a, F_D_a
 
+    def first_stage_maps(self, example):
+        """`forward_two_stage(return_loss=False)` up to the head maps (extract_feat, then the head): (neck map, detached head maps per
+        task) - what TwoStageDetector.forward_static hands to predict_static and the static second stage"""
+        prefix = "dense_" if "dense_voxels" in example else ""
+        data = dict(features=self._read(example, prefix), coors=example[prefix + "coordinates"], batch_size=len(example[prefix + "num_voxels"]),
+                    input_shape=example["shape"][0], bev_private=False)
+        x, _, _ = self.extract_feat(data)
+        return x, [{k: v.detach() for k, v in p.items()} for p in self._dense(self.bbox_head, x)]
+
 
 @DETECTORS.register_module
 class KD_VoxelNet(VoxelNet):
@@ -435,3 +444,16 @@ class KD_VoxelNet(VoxelNet):
         if return_loss:
             return boxes, x, voxel_feature, self.bbox_head.loss(example, preds)
         return boxes, x, voxel_feature, None, F_S_a, F_S_b
+
+    def first_stage_maps(self, example):
+        """`forward_two_stage(return_loss=False)` up to the head maps (the neck in eval mode, the PCR head not evaluated): (neck map,
+        detached head maps per task)"""
+        data = dict(features=self._read(example), coors=example["coordinates"], batch_size=len(example["num_voxels"]),
+                    input_shape=example["shape"][0])
+        was_training = self.neck.training
+        self.neck.eval()   # S2D_RPN builds its PCR outputs only in training mode
+        try:
+            x = self.extract_feat(data, train_pcm=False)[0]
+        finally:
+            self.neck.train(was_training)
+        return x, [{k: v.detach() for k, v in p.items()} for p in self._dense(self.bbox_head, x)]

@@ -29,7 +29,11 @@ copy; only the ROI_PER_IMAGE sampled RoIs get BEV features.  `TwoStageDetector.f
 
 RoI MLP at inference (csrc/roi_mlp.hip; `roi_mlp_reference`, `roi_mlp_fused`, `RoIHead.mlp_reason`): on the device path the eval-mode MLP - shared_fc_layer,
 cls_layers, reg_layers - is ONE fused fp32 MFMA launch from a packed weight image and a scale / shift vector cached on the head.  Training mode, a required
-gradient, a head outside the kernel's shape family or `S2D_ROI_MLP=0` keep the three nn.Sequential's; `head.mlp_paths` counts the calls of each."""
+gradient, a head outside the kernel's shape family or `S2D_ROI_MLP=0` keep the three nn.Sequential's; `head.mlp_paths` counts the calls of each.
+
+Static path (`StaticRoIPlan`, `TwoStageDetector.forward_static`; s2d_roi_pack_static, s2d_roi_refine_static): the inference second stage on the
+padded, device-counted detections of `CenterHead.predict_static`, every buffer allocated once, 4 launches with no host read - capturable into
+one HIP graph behind the static predict.  Opt-in; nothing above takes it by itself."""
 import ctypes
 import os
 
@@ -38,7 +42,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, registry
+from . import _lib, center_predict, registry
 from .registry import DETECTORS, ROI_HEAD, SECOND_STAGE
 
 ROI_MAX_GT = 512      # S2D_ROI_MAX_GT: ground-truth rows per sample that s2d_roi_match_gt stages in LDS
@@ -626,6 +630,13 @@ class RoIHead(nn.Module):
 
     def _mlp_check(self, feats):
         """(reason | None, spec)"""
+        cuda = torch.is_tensor(feats) and feats.is_cuda
+        return self._mlp_check_for(cuda, feats.dtype if cuda else None, feats.shape[-1] if cuda else None, feats.device if cuda else None,
+                                   bool(cuda and feats.requires_grad))
+
+    def _mlp_check_for(self, cuda, dtype, channels, device, feats_grad):
+        """`_mlp_check` from what it reads of the features: whether they are a CUDA tensor, their dtype, channel count and device, and
+        whether they require a gradient (StaticRoIPlan asks before its feature buffer exists)"""
         if os.environ.get("S2D_ROI_MLP") == "0":
             return "S2D_ROI_MLP=0", None
         if self.training:
@@ -633,19 +644,19 @@ class RoIHead(nn.Module):
         spec = self._mlp_spec()
         if isinstance(spec, str):
             return spec, None
-        if not (torch.is_tensor(feats) and feats.is_cuda):
+        if not cuda:
             return "the features are not a CUDA tensor (CPU tensor)", None
-        if feats.dtype != torch.float32:
-            return f"feature dtype {feats.dtype}", None
-        if feats.shape[-1] != spec[0]:
-            return f"{feats.shape[-1]} feature channels for a head of {spec[0]}", None
+        if dtype != torch.float32:
+            return f"feature dtype {dtype}", None
+        if channels != spec[0]:
+            return f"{channels} feature channels for a head of {spec[0]}", None
         tensors = []
         for conv, bn in spec[4]:
             tensors += [conv.weight, conv.bias] if bn is None else [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
         tensors = [t for t in tensors if t is not None]
-        if any(t.device != feats.device or t.dtype != torch.float32 for t in tensors):
+        if any(t.device != device or t.dtype != torch.float32 for t in tensors):
             return "parameters on another device or not fp32", None
-        if torch.is_grad_enabled() and (feats.requires_grad or any(t.requires_grad for t in tensors)):
+        if torch.is_grad_enabled() and (feats_grad or any(t.requires_grad for t in tensors)):
             return "a gradient is required (no backward through the fused MLP)", None
         return None, spec
 
@@ -738,6 +749,152 @@ class RoIHead(nn.Module):
         return batch_dict
 
 
+# ---- the second stage without the host: fixed-capacity buffers, launches only, capturable into one HIP graph behind predict_static -------
+STATIC_ROI_LAUNCHES = 4   # s2d_roi_pack_static, s2d_roi_bev_features, s2d_roi_mlp_run, s2d_roi_refine_static
+
+
+class StaticRefinedDetections(center_predict.StaticDetections):
+    """`StaticRoIPlan.run`'s results: a `StaticDetections` (boxes [B, cap, 7], scores, labels [B, cap], counts [B]; zero rows with label
+    -1 behind the counts; overflow = the first stage's, passed through) that also carries the example's `metadata`, which `as_list()`
+    then hands out without being given it."""
+    __slots__ = ("metadata",)
+
+    def __init__(self, boxes, scores, labels, counts, overflow=None, metadata=None):
+        super().__init__(boxes, scores, labels, counts, overflow)
+        self.metadata = metadata
+
+    def as_list(self, metadata=None):
+        """what `TwoStageDetector.forward(return_loss=False)` returns: one dict per sample (box3d_lidar, scores, label_preds,
+        metadata), views into the padded buffers.  The ONE host read of the static path: the counts."""
+        return super().as_list(self.metadata if metadata is None else metadata)
+
+
+class StaticRoIPlan:
+    """The inference second stage on `CenterHead.predict_static`'s padded, device-counted detections (center_predict.StaticDetections),
+    for one (RoI head MLP spec, BEVFeatureExtractor geometry, num_point, samples B, det_cap, cap = NMS_POST_MAXSIZE, map channels and
+    dtype, device).  Everything is allocated here, once: rois, roi_scores, roi_labels, row, counts, feats [B * cap, num_point * C],
+    rcnn_cls, rcnn_reg and the outputs; the MLP's packed weight image and scale / shift vector come from the head's `_mlp_images`.
+
+    `run(det, bev)` only launches on the current stream - s2d_roi_pack_static, s2d_roi_bev_features, s2d_roi_mlp_run,
+    s2d_roi_refine_static: 4 launches - with no host read, no host-to-device copy and, in the steady state, no allocation and no torch
+    operator, so it can be captured into a HIP graph (one stream, a linear chain), alone or behind StaticPredictPlan.run.  The boxes are
+    read where `det` holds them (the row table indexes det.boxes as [B * det_cap, 7]), the map where it lies with its own strides.
+
+    The MLP images are checked at every call on the host by the (data_ptr, _version) keys `_mlp_images` keeps: after an optimizer step,
+    load_state_dict or an in-place edit the stale image is rebuilt BEFORE the launches (such a call may allocate and runs torch
+    operators) and counted in `repacks`.  A graph captured earlier holds the old images' addresses: it must be captured again after the
+    weights change.
+
+    Refused with S2DError before any HIP call, no fallback: a non-CUDA device, B > 64, boxes that are not 7-column, a detection set of
+    another B or det_cap, a head whose `mlp_reason` is not None (training mode, a required gradient, a shape outside the kernel's
+    family), num_point other than 1 or 5, a code size other than 7 or more than one RoI class, second-stage modules other than one
+    BEVFeatureExtractor, a map of another dtype, channel count or batch."""
+
+    def __init__(self, roi_head, second_stage, num_point, samples, det_cap, cap, channels, map_dtype, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.S2DError("StaticRoIPlan: a CUDA device expected (no CPU fallback)")
+        if not 1 <= samples <= ROI_MAX_BATCH:
+            raise _lib.S2DError(f"StaticRoIPlan: {samples} samples (1..{ROI_MAX_BATCH} supported)")
+        if det_cap < 1 or cap < 1 or samples * det_cap >= 2 ** 31:
+            raise _lib.S2DError(f"StaticRoIPlan: det_cap {det_cap}, cap {cap} (>= 1 each, samples x det_cap below 2^31)")
+        if num_point not in (1, 5):
+            raise _lib.S2DError(f"StaticRoIPlan: num_point {num_point} (1 or 5 supported)")
+        if roi_head.code_size != 7 or roi_head.num_class != 1:
+            raise _lib.S2DError(f"StaticRoIPlan: code_size {roi_head.code_size}, num_class {roi_head.num_class} (code size 7 and one RoI class only)")
+        modules = list(second_stage)
+        if len(modules) != 1 or type(modules[0]) is not BEVFeatureExtractor:
+            raise _lib.S2DError("StaticRoIPlan: second-stage modules other than one BEVFeatureExtractor")
+        if map_dtype not in (torch.float32, torch.bfloat16) or channels < 1:
+            raise _lib.S2DError(f"StaticRoIPlan: a map of {channels} channels in {map_dtype} (fp32 or bf16)")
+        if device.index is None:   # (without a GPU the head's reason below is still given before any HIP call)
+            device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.head, self.device = roi_head, device
+        self.samples, self.det_cap, self.cap, self.num_point = int(samples), int(det_cap), int(cap), int(num_point)
+        self.channels, self.map_dtype, self.cin = int(channels), map_dtype, int(num_point) * int(channels)
+        reason, spec = roi_head._mlp_check_for(True, torch.float32, self.cin, device, False)
+        if reason is not None:
+            raise _lib.S2DError(f"StaticRoIPlan: {reason}")
+        ext = modules[0]
+        self.geo = (float(ext.pc_start[0]), float(ext.pc_start[1]), float(ext.voxel_size[0]), float(ext.voxel_size[1]), float(ext.out_stride))
+        _lib.load()
+        b, rows = self.samples, self.samples * self.cap
+        new = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+        self.rois, self.roi_scores, self.roi_labels = new((b, cap, 7), torch.float32), new((b, cap), torch.float32), new((b, cap), torch.int64)
+        self.row, self.counts = new((b, cap), torch.int32), new((b,), torch.int32)
+        self.feats = new((rows, self.cin), torch.float32)
+        self.rcnn_cls, self.rcnn_reg = new((rows, 1), torch.float32), new((rows, 7), torch.float32)
+        self.boxes, self.scores, self.labels = new((b, cap, 7), torch.float32), new((b, cap), torch.float32), new((b, cap), torch.int64)
+        self.out = StaticRefinedDetections(self.boxes, self.scores, self.labels, self.counts)
+        self.repacks = 0
+        self._mlp_plan, self._packed, self._affine = roi_head._mlp_images(spec, device)
+
+    def buffers(self):
+        """every device buffer the plan owns by name (none is ever reallocated; the MLP images belong to the head)"""
+        names = ("rois", "roi_scores", "roi_labels", "row", "counts", "feats", "rcnn_cls", "rcnn_reg", "boxes", "scores", "labels")
+        return {n: getattr(self, n) for n in names}
+
+    def _check(self, det, bev):
+        boxes, scores, labels, counts = det.boxes, det.scores, det.labels, det.counts
+        if boxes.dim() != 3 or boxes.shape[-1] != 7:
+            raise _lib.S2DError(f"StaticRoIPlan.run: boxes {tuple(boxes.shape)}: 7-column boxes [B, det_cap, 7] expected (the velocity columns of "
+                                "9-column first-stage boxes are not supported)")
+        b, d = self.samples, self.det_cap
+        if tuple(boxes.shape) != (b, d, 7):
+            raise _lib.S2DError(f"StaticRoIPlan.run: boxes {tuple(boxes.shape)}, the plan was built for {(b, d, 7)} (samples, det_cap, 7)")
+        for name, t, dtype, shape in (("boxes", boxes, torch.float32, (b, d, 7)), ("scores", scores, torch.float32, (b, d)),
+                                      ("labels", labels, torch.int64, (b, d)), ("counts", counts, torch.int32, (b,))):
+            if t.device != self.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise _lib.S2DError(f"StaticRoIPlan.run: {name} is {t.dtype} {tuple(t.shape)} on {t.device}"
+                                    f"{'' if t.is_contiguous() else ', not contiguous'}: contiguous {dtype} {shape} on {self.device} expected "
+                                    "(the static second stage neither copies nor converts)")
+        if not (torch.is_tensor(bev) and bev.dim() == 4 and bev.device == self.device):
+            raise _lib.S2DError(f"StaticRoIPlan.run: the neck map is not a [B, C, H, W] tensor on {self.device}")
+        if bev.dtype != self.map_dtype or bev.shape[0] != b or bev.shape[1] != self.channels or bev.shape[2] < 1 or bev.shape[3] < 1:
+            raise _lib.S2DError(f"StaticRoIPlan.run: the neck map is {bev.dtype} {tuple(bev.shape)}, the plan was built for {self.map_dtype} "
+                                f"[{b}, {self.channels}, H, W]")
+        if any(s < 0 for s in bev.stride()):
+            raise _lib.S2DError("StaticRoIPlan.run: a neck map with a negative stride")
+        reason, spec = self.head._mlp_check_for(True, torch.float32, self.cin, self.device, False)
+        if reason is not None:
+            raise _lib.S2DError(f"StaticRoIPlan.run: {reason}")
+        return spec
+
+    def run(self, det, bev):
+        """det: the StaticDetections of a StaticPredictPlan with this plan's samples and det_cap; bev [B, C, H, W] fp32 or bf16, NCHW or
+        channels_last, read in place.  Launches only, on the current stream; returns the plan's `StaticRefinedDetections` (the same
+        tensors at every call, overwritten by the next one)."""
+        spec = self._check(det, bev)   # host only
+        mlp_plan, packed, affine = self.head._mlp_images(spec, self.device)   # host only unless a key moved
+        if packed is not self._packed or affine is not self._affine:
+            self.repacks += 1
+            self._mlp_plan, self._packed, self._affine = mlp_plan, packed, affine
+        lib, st, ptr = _lib.load(), torch._C._cuda_getCurrentRawStream(self.device.index), lambda t: t.data_ptr()
+        b, d, cap, rows = self.samples, self.det_cap, self.cap, self.samples * self.cap
+        _lib.check(lib.s2d_roi_pack_static(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.counts), b, d, cap, ptr(self.rois),
+                                           ptr(self.roi_scores), ptr(self.roi_labels), ptr(self.row), ptr(self.counts), st), "s2d_roi_pack_static")
+        _lib.check(lib.s2d_roi_bev_features(ptr(bev), int(bev.dtype == torch.bfloat16), b, self.channels, bev.shape[2], bev.shape[3], *bev.stride(),
+                                            ptr(det.boxes), b * d, 7, ptr(self.row), cap, self.num_point, *self.geo, ptr(self.feats), st),
+                   "s2d_roi_bev_features")
+        _lib.check(lib.s2d_roi_mlp_run(ctypes.byref(mlp_plan), ptr(self.feats), rows, ptr(packed), ptr(affine), ptr(self.rcnn_cls),
+                                       ptr(self.rcnn_reg), st), "s2d_roi_mlp_run")
+        _lib.check(lib.s2d_roi_refine_static(ptr(self.rois), ptr(self.roi_scores), ptr(self.roi_labels), ptr(self.rcnn_cls), ptr(self.rcnn_reg),
+                                             ptr(self.counts), b, cap, ptr(self.boxes), ptr(self.scores), ptr(self.labels), st),
+                   "s2d_roi_refine_static")
+        self.out.overflow = det.overflow
+        return self.out
+
+
+def static_roi_plan_key(roi_head, second_stage, num_point, samples, det_cap, cap, channels, map_dtype, device):
+    """what a StaticRoIPlan depends on, as a hashable key (TwoStageDetector.forward_static caches plans by it)"""
+    spec = roi_head._mlp_spec()
+    shape = spec if isinstance(spec, str) else (spec[0], tuple(spec[1]), tuple(spec[2]), tuple(spec[3]))
+    geo = tuple((type(m).__name__, tuple(float(v) for v in getattr(m, "pc_start", ())), tuple(float(v) for v in getattr(m, "voxel_size", ())),
+                 float(getattr(m, "out_stride", 0))) for m in second_stage)
+    # (the plan holds the head it was built for - and so keeps its id from being reused: another head of the same shape gets its own plan)
+    return (id(roi_head), shape, geo, int(num_point), int(samples), int(det_cap), int(cap), int(channels), map_dtype, str(device))
+
+
 def box_side_centers(box3d):
     """centre + the four face-centre points of each BEV box (two_stage.py:50-74, box_torch_ops.center_to_corner_box2d):
     [5*n, 3], the five sets stacked along dim 0"""
@@ -771,6 +928,8 @@ class TwoStageDetector(nn.Module):
         self.roi_head = registry.build(roi_head, ROI_HEAD)
         self.num_point = num_point
         self.roi_paths = {"device": 0, "torch": 0}   # calls of forward() by the path their second stage took
+        self.static_calls = 0                        # calls of forward_static()
+        self._static_roi_plans = {}                  # StaticRoIPlan by static_roi_plan_key
 
     def train(self, mode=True):
         super().train(mode)
@@ -912,6 +1071,37 @@ class TwoStageDetector(nn.Module):
             n = offsets[b + 1] - offsets[b]
             out.append(dict(box3d_lidar=batch_dict["batch_box_preds"][b, :n], scores=batch_dict["refined_scores"][b, :n],
                             label_preds=batch_dict["refined_labels"][b, :n], metadata=meta[b] if meta else None))
+        return out
+
+    @torch.no_grad()
+    def forward_static(self, example, max_candidates=4096):
+        """Inference with both stages behind the head maps on the static path (opt-in; `forward`, `forward_two_stage`, `_forward_device`,
+        `roi_paths` and every environment switch are untouched; `static_calls` counts the calls):
+          1. the first stage up to the head maps, by the route `forward_two_stage` takes (`single_det.first_stage_maps`: extract_feat,
+             then the head);
+          2. `bbox_head.predict_static` (center_predict.StaticPredictPlan);
+          3. `StaticRoIPlan.run` on its detections and the neck map, the plan cached on the detector by `static_roi_plan_key`.
+        Returns the plan's StaticRefinedDetections - padded device tensors that the next call overwrites; `.as_list()` does the one host
+        read and gives what `forward(return_loss=False)` returns.  Only steps 2 and 3 are launches-only and can be captured into a HIP
+        graph (capture `StaticPredictPlan.run` + `StaticRoIPlan.run` on static input tensors): the sparse first stage is shape-dynamic.
+        Whatever either plan refuses is an S2DError here: there is no fallback to `forward`."""
+        bev, preds = self.single_det.first_stage_maps(example)
+        det, meta = self.bbox_head.predict_static(example, preds, self.single_det.test_cfg, max_candidates)
+        if not (torch.is_tensor(bev) and bev.dim() == 4):
+            raise _lib.S2DError("forward_static: the neck map is not a [B, C, H, W] tensor")
+        if det.boxes.dim() != 3:
+            raise _lib.S2DError(f"forward_static: first-stage boxes {tuple(det.boxes.shape)}")
+        bev = bev.detach()
+        samples, det_cap = det.boxes.shape[:2]
+        key = static_roi_plan_key(self.roi_head, self.second_stage, self.num_point, samples, det_cap, self.NMS_POST_MAXSIZE, bev.shape[1], bev.dtype,
+                                  bev.device)
+        plan = self._static_roi_plans.get(key)
+        if plan is None:
+            plan = self._static_roi_plans[key] = StaticRoIPlan(self.roi_head, self.second_stage, self.num_point, samples, det_cap,
+                                                               self.NMS_POST_MAXSIZE, bev.shape[1], bev.dtype, bev.device)
+        out = plan.run(det, bev)
+        out.metadata = meta
+        self.static_calls += 1
         return out
 
     def forward(self, example, return_loss=True, return_feature=False, **kwargs):
