@@ -1013,6 +1013,14 @@ int s2d_anchor_decode(const float *box_preds, const float *cls_preds, const floa
  * ((r - direction_offset) > 0) != (dir_label != 0) (mg_head.py:1057-1066), out_scores [segments][max_keep], out_labels
  * [segments][max_keep] (int64, class + the task's label_base; of the task records only label_base is read) and out_count [segments] -
  * written for EVERY segment; entries past out_count[s] are left untouched.
+ *
+ * s2d_anchor_predict_finish_static (the static path, anchor_predict.StaticAnchorPlan): the same finish with one workgroup per SAMPLE b.
+ * It walks the sample's tasks in task order, every segment s = task * samples + b as above (the same per-row arithmetic, bit for bit; a
+ * segment reaching outside [0, total) counts as empty), and writes the surviving rows contiguously from row 0 of out_boxes
+ * [samples][cap][7], out_scores [samples][cap], out_labels [samples][cap] (int64), cap = num_tasks * max_keep, and their number into
+ * out_counts [samples] (int32).  Rows at or past out_counts[b] are written at every call: boxes and scores zero, label -1.  No atomics,
+ * no communication between workgroups.  Refused with S2D_ERR_ARG before any HIP call: a null pointer, num_tasks outside 1..8, a negative
+ * size, num_tasks * samples > 65535; samples == 0 succeeds without a launch.
  */
 #define S2D_ANCHOR_PREDICT_MAX_TASKS 8
 typedef struct s2d_anchor_predict_task {
@@ -1032,6 +1040,11 @@ int s2d_anchor_predict_finish(const s2d_anchor_predict_task *tasks, int num_task
                               const int32_t *counts, int64_t total, const int64_t *keep, const int32_t *n_keep, int max_keep,
                               int use_direction, float direction_offset, float *out_boxes, float *out_scores,
                               int64_t *out_labels, int32_t *out_count, s2d_stream_t stream);
+int s2d_anchor_predict_finish_static(const s2d_anchor_predict_task *tasks, int num_tasks, int samples, const float *boxes,
+                                     const float *scores, const int32_t *labels, const int32_t *dir_labels, const uint8_t *in_range,
+                                     const int32_t *offsets, const int32_t *counts, int64_t total, const int64_t *keep,
+                                     const int32_t *n_keep, int max_keep, int use_direction, float direction_offset, float *out_boxes,
+                                     float *out_scores, int64_t *out_labels, int32_t *out_counts, s2d_stream_t stream);
 
 /*
  * Optimizer step of the reference's training loop (det3d/torchie/apis/train.py:168-186, det3d/solver/fastai_optim.py:158-171,

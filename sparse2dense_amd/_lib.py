@@ -449,6 +449,8 @@ SIGNATURES = {
                                  [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 6),
     "s2d_anchor_predict_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int64] +
                                   [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 5),
+    "s2d_anchor_predict_finish_static": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_int64] +
+                                         [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 5),
     # deformable convolution v1 (csrc/deform_conv.hip)
     "s2d_deform_conv_supported": (ctypes.c_int, [ctypes.c_int] * 9),
     "s2d_deform_conv_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 7),

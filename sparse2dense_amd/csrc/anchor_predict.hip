@@ -11,6 +11,9 @@
 //   anchor_finish_kernel   one workgroup per segment walks its keep list: drops the rows outside post_center_limit_range (AFTER the NMS, as
 //                          the reference does: a box outside the range still suppresses), restores the heading sign, applies the direction
 //                          flip, adds the task's label base and writes the padded per-segment outputs and their count
+//   anchor_finish_static_kernel  (the static path, anchor_predict.StaticAnchorPlan: s2d_segment_topk of segment_topk.hip in place of
+//                          the sort, no host read) the same finish with one workgroup per SAMPLE: its tasks in task order, compacted
+//                          into [samples][tasks * max_keep] outputs whose padding rows are written too
 // The per-task pointers travel by value in the kernel arguments (s2d_anchor_predict_task[8]).  The decode expressions are the ones of
 // anchor_decode_kernel (anchor_decode.h); the library is built with -ffp-contract=off, so both paths give the same bits.
 // Built without the SLP vectoriser (DESIGN rule 36), as center_predict.hip is: predict may run beside a side stream's MFMA kernels.
@@ -85,6 +88,26 @@ struct AnchorFinish {
     int label_base[AP_MAX_TASKS];
 };
 
+// One kept row of the packed lists -> row `out` of the outputs: the heading sign restored, the direction flip, the task's label base.
+// anchor_finish_kernel and anchor_finish_static_kernel both call it, so the two give the same bits.
+__device__ __forceinline__ void anchor_finish_row(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                  const int32_t *__restrict__ labels, const int32_t *__restrict__ dirs, int64_t row,
+                                                  const AnchorFinish &g, int base_label, int64_t out, float *__restrict__ out_boxes,
+                                                  float *__restrict__ out_scores, int64_t *__restrict__ out_labels) {
+    const float *bx = boxes + row * 7;
+    float *o = out_boxes + out * 7;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) o[e] = bx[e];
+    float r = -bx[6];
+    if (g.use_dir) {   // mg_head.py:1057-1066: the heading and the direction classifier disagree -> the opposite heading
+        const bool opposite = ((r - g.dir_offset) > 0.f) != (dirs[row] != 0);
+        r = r + (opposite ? (float)3.141592653589793 : 0.f);
+    }
+    o[6] = r;
+    out_scores[out] = scores[row];
+    out_labels[out] = (int64_t)labels[row] + base_label;
+}
+
 __global__ __launch_bounds__(256) void anchor_finish_kernel(const float *__restrict__ boxes, const float *__restrict__ scores,
                                                             const int32_t *__restrict__ labels, const int32_t *__restrict__ dirs,
                                                             const uint8_t *__restrict__ in_range, const int32_t *__restrict__ offsets,
@@ -116,23 +139,63 @@ __global__ __launch_bounds__(256) void anchor_finish_kernel(const float *__restr
         __syncthreads();
         int pos = written + before;
         for (int w = 0; w < wave; ++w) pos += wave_total[w];
-        if (stay) {
-            const float *bx = boxes + row * 7;
-            float *o = out_boxes + ((int64_t)seg * g.max_keep + pos) * 7;
-#pragma unroll
-            for (int e = 0; e < 6; ++e) o[e] = bx[e];
-            float r = -bx[6];
-            if (g.use_dir) {   // mg_head.py:1057-1066: the heading and the direction classifier disagree -> the opposite heading
-                const bool opposite = ((r - g.dir_offset) > 0.f) != (dirs[row] != 0);
-                r = r + (opposite ? (float)3.141592653589793 : 0.f);
-            }
-            o[6] = r;
-            out_scores[(int64_t)seg * g.max_keep + pos] = scores[row];
-            out_labels[(int64_t)seg * g.max_keep + pos] = (int64_t)labels[row] + base_label;
-        }
+        if (stay)
+            anchor_finish_row(boxes, scores, labels, dirs, row, g, base_label, (int64_t)seg * g.max_keep + pos, out_boxes, out_scores, out_labels);
         written += wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
     }
     if (threadIdx.x == 0) out_count[seg] = written;
+}
+
+// The finish of the static path (anchor_predict.StaticAnchorPlan): one workgroup per SAMPLE walks its tasks in task order, every segment
+// as anchor_finish_kernel walks it, and compacts the surviving rows from row 0 of the sample's cap = tasks * max_keep output rows - the
+// write position is carried on across the tasks.  The rows behind the sample's count are written as well (zero boxes and scores, label
+// -1), so the outputs are a function of the inputs alone.  No atomics, no communication between workgroups.
+__global__ __launch_bounds__(256) void anchor_finish_static_kernel(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                                   const int32_t *__restrict__ labels, const int32_t *__restrict__ dirs,
+                                                                   const uint8_t *__restrict__ in_range, const int32_t *__restrict__ offsets,
+                                                                   const int32_t *__restrict__ counts, int64_t total,
+                                                                   const int64_t *__restrict__ keep, const int32_t *__restrict__ n_keep,
+                                                                   AnchorFinish g, int num_tasks, float *__restrict__ out_boxes,
+                                                                   float *__restrict__ out_scores, int64_t *__restrict__ out_labels,
+                                                                   int32_t *__restrict__ out_counts) {
+    __shared__ int wave_total[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t cap = (int64_t)num_tasks * g.max_keep, first = b * cap;
+    int written = 0;   // uniform over the block; at most cap: every segment adds at most max_keep
+    for (int task = 0; task < num_tasks; ++task) {
+        const int seg = task * g.samples + b;
+        const int64_t off = offsets[seg];
+        int rows = counts[seg], n = min(n_keep[seg], g.max_keep);
+        if (rows < 0 || off < 0 || off + rows > total) rows = 0;   // a segment outside the packed lists counts as empty
+        if (rows == 0 || n < 0) n = 0;
+        const int base_label = g.label_base[task];
+        for (int start = 0; start < n; start += 256) {
+            const int i = start + threadIdx.x;
+            int64_t row = -1;
+            if (i < n) {
+                const int64_t k = keep[(int64_t)seg * g.max_keep + i];
+                if (k >= 0 && k < rows) row = off + k;
+            }
+            const bool stay = row >= 0 && in_range[row] != 0;
+            const unsigned long long votes = __ballot(stay);
+            const int before = (int)__popcll(votes & ((1ull << lane) - 1ull));
+            __syncthreads();   // (the previous chunk's reads of wave_total are done)
+            if (lane == 0) wave_total[wave] = (int)__popcll(votes);
+            __syncthreads();
+            int pos = written + before;
+            for (int w = 0; w < wave; ++w) pos += wave_total[w];
+            if (stay) anchor_finish_row(boxes, scores, labels, dirs, row, g, base_label, first + pos, out_boxes, out_scores, out_labels);
+            written += wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
+        }
+    }
+    for (int64_t i = written + threadIdx.x; i < cap; i += 256) {
+        float *o = out_boxes + (first + i) * 7;
+#pragma unroll
+        for (int e = 0; e < 7; ++e) o[e] = 0.f;
+        out_scores[first + i] = 0.f;
+        out_labels[first + i] = -1;
+    }
+    if (threadIdx.x == 0) out_counts[b] = written;
 }
 
 static int check_anchor_tasks(const char *what, const s2d_anchor_predict_task *tasks, int num_tasks, int samples, int64_t max_anchors,
@@ -217,6 +280,27 @@ extern "C" int s2d_anchor_predict_finish(const s2d_anchor_predict_task *tasks, i
     for (int i = 0; i < num_tasks; ++i) g.label_base[i] = tasks[i].label_base;
     hipLaunchKernelGGL(anchor_finish_kernel, dim3((unsigned)segs), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels, dir_labels, in_range,
                        offsets, counts, total, keep, n_keep, g, out_boxes, out_scores, out_labels, out_count);
+    S2D_LAUNCH_CHECK();
+    return S2D_OK;
+}
+
+extern "C" int s2d_anchor_predict_finish_static(const s2d_anchor_predict_task *tasks, int num_tasks, int samples, const float *boxes,
+                                                const float *scores, const int32_t *labels, const int32_t *dir_labels, const uint8_t *in_range,
+                                                const int32_t *offsets, const int32_t *counts, int64_t total, const int64_t *keep,
+                                                const int32_t *n_keep, int max_keep, int use_direction, float direction_offset, float *out_boxes,
+                                                float *out_scores, int64_t *out_labels, int32_t *out_counts, s2d_stream_t stream) {
+    S2D_CHECK_ARG(tasks, "anchor_predict_finish_static: null task table");
+    S2D_CHECK_ARG(num_tasks >= 1 && num_tasks <= AP_MAX_TASKS, "anchor_predict_finish_static: %d tasks (1..%d supported)", num_tasks, AP_MAX_TASKS);
+    S2D_CHECK_ARG(samples >= 0 && (int64_t)num_tasks * samples <= 65535, "anchor_predict_finish_static: bad samples %d", samples);
+    S2D_CHECK_ARG(total >= 0 && max_keep >= 0, "anchor_predict_finish_static: negative size (total %lld, max_keep %d)", (long long)total, max_keep);
+    if (samples == 0) return S2D_OK;
+    S2D_CHECK_ARG(offsets && counts && n_keep && out_counts, "anchor_predict_finish_static: null segment arrays or out_counts");
+    S2D_CHECK_ARG(boxes && scores && labels && dir_labels && in_range && keep, "anchor_predict_finish_static: null input");
+    S2D_CHECK_ARG(out_boxes && out_scores && out_labels, "anchor_predict_finish_static: null output");
+    AnchorFinish g{samples, max_keep, use_direction != 0, direction_offset, {0, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < num_tasks; ++i) g.label_base[i] = tasks[i].label_base;
+    hipLaunchKernelGGL(anchor_finish_static_kernel, dim3((unsigned)samples), dim3(256), 0, (hipStream_t)stream, boxes, scores, labels, dir_labels,
+                       in_range, offsets, counts, total, keep, n_keep, g, num_tasks, out_boxes, out_scores, out_labels, out_counts);
     S2D_LAUNCH_CHECK();
     return S2D_OK;
 }

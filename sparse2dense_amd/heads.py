@@ -9,7 +9,8 @@
 
 `CenterHead.predict` (decode + rotated / circle NMS) runs on the device through center_predict.py for CUDA
 maps; `CenterHead.predict_torch` is the per-segment torch chain it replaced.  `MultiGroupHead.predict` likewise through
-anchor_predict.py, with `MultiGroupHead.predict_torch` as the chain.
+anchor_predict.py, with `MultiGroupHead.predict_torch` as the chain.  Both heads have an opt-in `predict_static`: the same predict as
+launches only, on buffers allocated once (center_predict.StaticPredictPlan, anchor_predict.StaticAnchorPlan).
 """
 import copy
 import ctypes
@@ -1211,6 +1212,8 @@ class MultiGroupHead(nn.Module):
         self.loss_norm, self.loss_cls, self.loss_reg, self.loss_aux = loss_norm, loss_cls, loss_bbox, loss_aux
         self.bev_only = mode == "bev"
         self.predict_paths = {"device": 0, "torch": 0}   # calls of predict() by the path they took
+        self.static_predict_calls = 0   # calls of predict_static() (opt-in: predict() never takes it)
+        self._static_plans = {}
         self.tasks = nn.ModuleList()
         for num_c, num_a in zip(num_classes, self.num_anchor_per_locs):
             num_cls = num_a * num_c if encode_background_as_zeros else num_a * (num_c + 1)
@@ -1308,6 +1311,31 @@ class MultiGroupHead(nn.Module):
                         for i, (b, s, l) in enumerate(per_sample)]
         paths["torch"] += 1
         return self.predict_torch(example, preds_dicts, test_cfg, **kwargs)
+
+    @torch.no_grad()
+    def predict_static(self, example, preds_dicts, test_cfg, **kwargs):
+        """`predict` without the host (anchor_predict.StaticAnchorPlan: launches only, fixed-capacity outputs, capturable into a HIP
+        graph).  Opt-in; the plans are cached on the head, one per (test_cfg, class counts, anchor tables, samples, direction settings,
+        device).  Returns (StaticDetections, metadata): padded device tensors owned by the plan - the next call with the same plan
+        overwrites them - and the example's metadata; `detections.as_list(metadata)` gives what `predict` returns, with one host read.
+        Raises what `predict` raises for an unsupported option; refused with S2DError before any HIP call: nms_pre_max_size None or
+        outside 1..4096, more than 8 tasks, CPU tensors, predictions or anchor tables that are not fp32 and contiguous, a missing
+        dir_cls_preds under the direction classifier.  static_predict_calls counts the calls."""
+        from . import anchor_predict
+        self._check_supported("predict", example, kwargs)
+        self._check_test_cfg(test_cfg)
+        if not 1 <= len(preds_dicts) <= anchor_predict.MAX_TASKS:
+            raise anchor_predict._lib.S2DError(f"predict_static: {len(preds_dicts)} tasks (1..{anchor_predict.MAX_TASKS} supported)")
+        anchors = [self._task_anchors(example, t) for t in range(len(preds_dicts))]
+        samples, dev = anchor_predict._static_inputs(preds_dicts, anchors, self.use_direction_classifier)
+        key = anchor_predict.static_plan_key(test_cfg, self.num_classes, anchors, samples, self.use_direction_classifier, self.direction_offset, dev)
+        plan = self._static_plans.get(key)
+        if plan is None:
+            plan = self._static_plans[key] = anchor_predict.StaticAnchorPlan(test_cfg, self.num_classes, anchors, samples,
+                                                                             self.use_direction_classifier, self.direction_offset, dev)
+        out = plan.run(preds_dicts)
+        self.static_predict_calls += 1
+        return out, (example.get("metadata") if isinstance(example, dict) else None)
 
     @torch.no_grad()
     def predict_torch(self, example, preds_dicts, test_cfg, **kwargs):
