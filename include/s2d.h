@@ -1336,6 +1336,51 @@ int s2d_roi_mlp_run(const s2d_roi_mlp_plan *plan, const float *feats, int64_t ro
                     float *rcnn_reg, s2d_stream_t stream);
 
 /*
+ * The TRAINING branch of the same MLP (csrc/roi_mlp_train.hip): forward with batch statistics and caller-supplied dropout masks, the two RoI
+ * losses, and the backward of all of it, fp32 on the matrix cores, one launch per depth (a batch norm couples all rows).  The plan and the
+ * packed image are those of s2d_roi_mlp_plan_make / s2d_roi_mlp_pack; args holds, per layer of the plan's table, the UNPACKED weight
+ * [cout][cin], then for a hidden layer gamma, beta, the running statistics (moved in place: momentum, unbiased variance), the 0/1 byte mask
+ * [rows][cout] of the dropout site behind it (NULL: none) with keep_scale = 1 / (1 - p), and for a final layer its bias; the d_* pointers
+ * receive the gradients (backward only).  Shape family: that of s2d_roi_mlp_supported, 2 <= rows <= 8192, dropout ratio < 1.
+ * Hidden layer: z = a . W^T, mean / biased variance over the rows (per-tile mean and M2 merged in tile order with Chan's formula),
+ * a' = relu(gamma * (z - mean) / sqrt(var + eps) + beta) * mask * keep_scale.  The features get no gradient.
+ * The workspace (s2d_roi_mlp_train_scratch_bytes; 0 for a bad plan or row count) carries z, the statistics, dy and the per-tile backward
+ * sums from the forward to the backward call; every word is written before it is read.  No atomics, no zero-fill: same inputs, same bits.
+ * s2d_roi_mlp_train_launches: the kernel launches of one forward and one backward call.
+ *
+ * s2d_roi_loss_forward: out[0] = w_cls * sum over rows with labels >= 0 of BCE(sigmoid(rcnn_cls), labels) / max(valid, 1), logarithms
+ * clamped at -100 as torch does; out[1] = w_reg * sum over rows with fg > 0 of |rcnn_reg - target| . code_weights / max(fg rows, 1);
+ * out[2], out[3] = the two counts.  labels, fg [rows] fp32, target [rows][7]; code_weights = HOST array of 7.  s2d_roi_loss_backward:
+ * torch's gradients of the two for the upstream DEVICE scalars g_cls, g_reg: (p - y) / max(p (1 - p), 1e-12) * p (1 - p) and sign().
+ */
+typedef struct s2d_roi_mlp_train_layer {
+    const float *weight, *gamma, *beta;
+    float *running_mean, *running_var;
+    const float *bias;
+    const uint8_t *mask;
+    float *d_weight, *d_gamma, *d_beta, *d_bias;
+    float keep_scale, momentum, eps;
+    int32_t reserved;
+} s2d_roi_mlp_train_layer;
+typedef struct s2d_roi_mlp_train_args {
+    s2d_roi_mlp_train_layer layer[S2D_ROI_MLP_MAX_LAYERS];
+} s2d_roi_mlp_train_args;
+int s2d_roi_mlp_train_supported(int cin, int n_shared, int s0, int s1, int n_cls, int c0, int c1, int n_reg, int r0, int r1, int num_class,
+                                int code_size, int64_t rows, float dp_ratio);
+size_t s2d_roi_mlp_train_scratch_bytes(const s2d_roi_mlp_plan *plan, int64_t rows);
+int s2d_roi_mlp_train_launches(const s2d_roi_mlp_plan *plan, int *forward, int *backward);
+int s2d_roi_mlp_train_forward(const s2d_roi_mlp_plan *plan, const s2d_roi_mlp_train_args *args, const float *feats, int64_t rows,
+                              const float *packed, void *workspace, size_t workspace_bytes, float *rcnn_cls, float *rcnn_reg,
+                              s2d_stream_t stream);
+int s2d_roi_mlp_train_backward(const s2d_roi_mlp_plan *plan, const s2d_roi_mlp_train_args *args, const float *feats, int64_t rows,
+                               void *workspace, size_t workspace_bytes, const float *d_rcnn_cls, const float *d_rcnn_reg, s2d_stream_t stream);
+int s2d_roi_loss_forward(const float *rcnn_cls, const float *rcnn_reg, const float *labels, const float *fg, const float *target, int64_t rows,
+                         const float *code_weights, float w_cls, float w_reg, float *out, s2d_stream_t stream);
+int s2d_roi_loss_backward(const float *rcnn_cls, const float *rcnn_reg, const float *labels, const float *fg, const float *target, int64_t rows,
+                          const float *code_weights, float w_cls, float w_reg, const float *out, const float *g_cls, const float *g_reg,
+                          float *d_rcnn_cls, float *d_rcnn_reg, s2d_stream_t stream);
+
+/*
  * Frame preparation of the S2D data step (csrc/prep.hip; det3d/datasets/pipelines/preprocess.py:81-117,178-201,257-260).  points
  * [n_points][ncols] and obj_points [obj_rows][ncols] fp32 with x, y, z first; boxes [num_boxes][box_dim] fp32 with the centre in
  * columns 0-2, the size in 3-5 and the yaw in the LAST column; num_boxes <= S2D_PREP_MAX_BOXES, row counts <= S2D_PREP_MAX_POINTS.

@@ -45,6 +45,17 @@ class RoiMlpPlan(ctypes.Structure):
                [("affine_elems", ctypes.c_int32), ("reserved", ctypes.c_int32), ("layer", RoiMlpLayer * 8)]
 
 
+class RoiMlpTrainLayer(ctypes.Structure):
+    """s2d_roi_mlp_train_layer of include/s2d.h: the tensors of one layer of the RoI MLP's training branch"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("weight", "gamma", "beta", "running_mean", "running_var", "bias", "mask", "d_weight", "d_gamma", "d_beta",
+                                               "d_bias")] + [(n, ctypes.c_float) for n in ("keep_scale", "momentum", "eps")] + [("reserved", ctypes.c_int32)]
+
+
+class RoiMlpTrainArgs(ctypes.Structure):
+    """s2d_roi_mlp_train_args of include/s2d.h"""
+    _fields_ = [("layer", RoiMlpTrainLayer * 8)]
+
+
 # name -> (restype, argtypes); mirrors include/s2d.h one to one
 SIGNATURES = {
     "s2d_version": (ctypes.c_int, []),
@@ -483,6 +494,18 @@ SIGNATURES = {
     "s2d_roi_mlp_plan_make": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.POINTER(RoiMlpPlan)]),
     "s2d_roi_mlp_pack": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]),
     "s2d_roi_mlp_run": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    # its training branch: forward with batch statistics, the RoI losses and the backward (csrc/roi_mlp_train.hip)
+    "s2d_roi_mlp_train_supported": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_int64, ctypes.c_float]),
+    "s2d_roi_mlp_train_scratch_bytes": (ctypes.c_size_t, [ctypes.POINTER(RoiMlpPlan), ctypes.c_int64]),
+    "s2d_roi_mlp_train_launches": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "s2d_roi_mlp_train_forward": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.POINTER(RoiMlpTrainArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_roi_mlp_train_backward": (ctypes.c_int, [ctypes.POINTER(RoiMlpPlan), ctypes.POINTER(RoiMlpTrainArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_roi_loss_forward": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "s2d_roi_loss_backward": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float] +
+                              [ctypes.c_void_p] * 6),
     # frame preparation: inside test, dense / reconstruction clouds, global noise, shuffle gather (csrc/prep.hip)
     "s2d_prep_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "s2d_prep_points_in_rbbox": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

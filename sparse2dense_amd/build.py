@@ -29,6 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # roi_head.hip likewise: its fp32 bilinear blends run in the same step, right behind predict (rule 36).
 # anchor_predict.hip is MultiGroupHead.predict's counterpart of center_predict.hip and is built like it (rule 36).
 # roi_mlp.hip: its scale / shift epilogue is a packed-FP32 candidate and it runs between roi_head.hip's launches (rule 36).
+# roi_mlp_train.hip: the same MLP's training branch - norm, mask and gradient transforms are packed-FP32 candidates, same place in the step (rule 36).
 # pillar_distill.hip: eight channels of fp32 differences, squares and sums per thread are packed-FP32 candidates, and the pillar student's
 # backward reaches its gradient kernel while weight gradients of the PCR head can still run on the side stream (rule 36).
 # prep.hip: the inside test and the rotations are pairs of fp32 products and sums, packed-FP32 candidates, and the frame of step k + 1 is
@@ -37,7 +38,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # eval_ap.hip: every overlap decision rests on fp32 products and sums of the rectangle intersection rounded one by one, as nms.hip's.
 EXTRA = {"eval_ap.hip": ["-fno-slp-vectorize"], "deform_conv.hip": ["-fno-slp-vectorize"], "center_predict.hip": ["-fno-slp-vectorize"], "roi_head.hip": ["-fno-slp-vectorize"],
          "anchor_predict.hip": ["-fno-slp-vectorize"], "roi_mlp.hip": ["-fno-slp-vectorize"], "pillar_distill.hip": ["-fno-slp-vectorize"],
-         "prep.hip": ["-fno-slp-vectorize"], "tracking.hip": ["-fno-slp-vectorize"]}
+         "prep.hip": ["-fno-slp-vectorize"], "tracking.hip": ["-fno-slp-vectorize"], "roi_mlp_train.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("S2D_BUILD_LOSSES_SLP") != "1":
     EXTRA["losses.hip"] = ["-fno-slp-vectorize"]
 

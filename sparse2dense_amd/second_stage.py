@@ -31,6 +31,11 @@ RoI MLP at inference (csrc/roi_mlp.hip; `roi_mlp_reference`, `roi_mlp_fused`, `R
 cls_layers, reg_layers - is ONE fused fp32 MFMA launch from a packed weight image and a scale / shift vector cached on the head.  Training mode, a required
 gradient, a head outside the kernel's shape family or `S2D_ROI_MLP=0` keep the three nn.Sequential's; `head.mlp_paths` counts the calls of each.
 
+RoI head training (csrc/roi_mlp_train.hip; `roi_mlp_train_reference`, `roi_loss_reference`, `roi_mlp_train_fused`, `roi_loss_fused`, `RoIHead.fused_training`,
+`train_mlp_reason`, `train_paths`): opt-in, the training-mode MLP (batch statistics, dropout masks drawn in one call), the two RoI losses and the backward of all
+of it on fp32 MFMA kernels, one launch per depth, with no host read between the first forward and the last backward launch.  Off by default: nothing above
+changes unless `head.fused_training` is set.
+
 Static path (`StaticRoIPlan`, `TwoStageDetector.forward_static`; s2d_roi_pack_static, s2d_roi_refine_static): the inference second stage on the
 padded, device-counted detections of `CenterHead.predict_static`, every buffer allocated once, 4 launches with no host read - capturable into
 one HIP graph behind the static predict.  Opt-in; nothing above takes it by itself."""
@@ -301,6 +306,247 @@ def roi_mlp_fused(head, feats):
     return head._mlp_fused(feats, spec)
 
 
+# ---- the training branch of the RoI MLP: float64 definitions, then the kernels of csrc/roi_mlp_train.hip ---------------------------------
+ROI_MLP_TRAIN_ROWS = (2, 8192)   # s2d_roi_mlp_train_supported
+
+
+def _mlp_dropouts(seq):
+    """the nn.Dropout behind each (conv, batch norm) group of `_mlp_chain(seq)`, or None where the module has none: the dropout sites are
+    the module's own (RoIHead.__init__ / make_fc_layers, with the reference's `dp_ratio >= 0` / `> 0` asymmetry)"""
+    out, mods = [], list(seq)
+    for i, m in enumerate(mods):
+        if isinstance(m, nn.Conv1d):
+            j = i + 1
+            while j < len(mods) and isinstance(mods[j], (nn.BatchNorm1d, nn.ReLU)):
+                j += 1
+            out.append(mods[j] if j < len(mods) and isinstance(mods[j], nn.Dropout) else None)
+    return out
+
+
+def roi_mlp_train_sites(head):
+    """[(width, p)] of the dropout sites of `head` in the order shared, cls, reg - the order of the `masks` of the functions below"""
+    sites = []
+    for seq in (head.shared_fc_layer, head.cls_layers, head.reg_layers):
+        for (conv, _), dp in zip(_mlp_chain(seq), _mlp_dropouts(seq)):
+            if dp is not None:
+                sites.append((conv.out_channels, dp.p))
+    return sites
+
+
+def roi_mlp_train_reference(head, feats, masks=None):
+    """The TRAINING-mode MLP of `head` restated from its parameters: feats [..., cin] -> (rcnn_cls [R, 1], rcnn_reg [R, code], stats).
+    A hidden layer is z = a . W^T, mean and biased variance of z over the R rows, y = gamma * (z - mean) / sqrt(var + eps) + beta,
+    a' = relu(y), and behind a dropout site a' = a' * mask / (1 - p) with the caller's 0/1 mask [R, width] of that site (`masks`: one per
+    site in the order of `roi_mlp_train_sites`; None = no dropout).  The final layers carry their bias.  Differentiable by autograd;
+    `stats` = per hidden layer (shared, cls, reg) the batch mean and the UNBIASED variance the running statistics move toward (detached).
+    Does not touch the running statistics.  Any dtype: in float64 the oracle csrc/roi_mlp_train.hip is tested against."""
+    stats, site = [], [0]
+
+    def run(seq, x):
+        chain = _mlp_chain(seq)
+        if chain is None:
+            raise NotImplementedError("roi_mlp_train_reference: a chain of Conv1d(kernel_size=1) [+ BatchNorm1d + ReLU] groups expected")
+        for (conv, bn), dp in zip(chain, _mlp_dropouts(seq)):
+            z = F.linear(x, conv.weight.squeeze(-1), conv.bias)
+            if bn is None:
+                x = z
+                continue
+            mean, var = z.mean(dim=0), z.var(dim=0, unbiased=False)
+            stats.append((mean.detach(), z.var(dim=0, unbiased=True).detach()))
+            x = F.relu(bn.weight * (z - mean) / torch.sqrt(var + bn.eps) + bn.bias)
+            if dp is not None:
+                if masks is not None:
+                    x = x * masks[site[0]].to(x) / (1 - dp.p)
+                site[0] += 1
+        return x
+    shared = run(head.shared_fc_layer, feats.reshape(-1, feats.shape[-1]))
+    return run(head.cls_layers, shared), run(head.reg_layers, shared), stats
+
+
+class _BceOfSigmoid(torch.autograd.Function):
+    """F.binary_cross_entropy(sigmoid(x), y, reduction="none") as torch computes it and differentiates it: logarithms clamped at -100
+    forward; (p - y) / max(p (1 - p), 1e-12) * p (1 - p) backward - zero where the sigmoid has saturated, not 0 * inf"""
+    @staticmethod
+    def forward(ctx, x, y):
+        p = torch.sigmoid(x)
+        ctx.save_for_backward(p, y)
+        return -(y * torch.clamp(torch.log(p), min=-100.0) + (1 - y) * torch.clamp(torch.log(1 - p), min=-100.0))
+
+    @staticmethod
+    def backward(ctx, g):
+        p, y = ctx.saved_tensors
+        v = p * (1 - p)
+        return g * (p - y) / torch.clamp(v, min=1e-12) * v, None
+
+
+def _loss_cfg(loss_cfg):
+    w = _cfg_get(loss_cfg, "LOSS_WEIGHTS")
+    if _cfg_get(loss_cfg, "CLS_LOSS") != "BinaryCrossEntropy" or _cfg_get(loss_cfg, "REG_LOSS") != "L1":
+        raise NotImplementedError(f"RoI losses {_cfg_get(loss_cfg, 'CLS_LOSS')} / {_cfg_get(loss_cfg, 'REG_LOSS')} (BinaryCrossEntropy and L1 only)")
+    return [float(c) for c in w["code_weights"]], float(w["rcnn_cls_weight"]), float(w["rcnn_reg_weight"])
+
+
+def roi_loss_reference(rcnn_cls, rcnn_reg, cls_labels, reg_valid_mask, gt_of_rois, loss_cfg):
+    """(loss_cls, loss_reg) of RoIHead.get_box_cls_layer_loss (BinaryCrossEntropy) and get_box_reg_layer_loss (L1) as torch computes them,
+    in the dtype of the predictions: p = sigmoid(x), per row -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)) masked by label >= 0
+    and divided by clamp(valid, min=1); |reg - target| times code_weights masked by reg_valid_mask > 0 and divided by max(fg, 1); each
+    times its weight.  Labels may be soft (roi_iou) or hard with -1."""
+    code_weights, w_cls, w_reg = _loss_cfg(loss_cfg)
+    x = rcnn_cls.reshape(-1)
+    y = cls_labels.reshape(-1).to(x.dtype)
+    valid = (y >= 0).to(x.dtype)
+    loss_cls = (_BceOfSigmoid.apply(x, y) * valid).sum() / torch.clamp(valid.sum(), min=1.0) * w_cls
+    code = rcnn_reg.shape[-1]
+    fg = (reg_valid_mask.reshape(-1) > 0).to(x.dtype)
+    target = gt_of_rois[..., 0:code].reshape(-1, code).to(x.dtype)
+    l1 = (rcnn_reg.reshape(-1, code) - target).abs() * rcnn_reg.new_tensor(code_weights[:code])
+    loss_reg = (l1 * fg.unsqueeze(-1)).sum() / torch.clamp(fg.sum(), min=1.0) * w_reg
+    return loss_cls, loss_reg
+
+
+def _roi_train_workspace(floats, dev):
+    """the scratch that carries z, the statistics and the backward sums from s2d_roi_mlp_train_forward to _backward: uninitialised - every
+    word is written before it is read (tests replace this to fill it with NaN)"""
+    return torch.empty((floats,), dtype=torch.float32, device=dev)
+
+
+class _RoiMlpTrain(torch.autograd.Function):
+    """csrc/roi_mlp_train.hip: s2d_roi_mlp_train_forward / _backward.  Inputs behind `mask` are the parameters in the order of the plan's
+    layer table: weight, then (gamma, beta) of a hidden layer or the bias of a final one."""
+    @staticmethod
+    def forward(ctx, head, spec, x, mask, *params):
+        lib, dev, st = _device_args("roi_mlp_train", x)
+        plan, packed, _ = head._mlp_images(spec, dev, affine=False)
+        rows = x.shape[0]
+        args = _lib.RoiMlpTrainArgs()
+        drops = [d for seq in (head.shared_fc_layer, head.cls_layers, head.reg_layers) for d in _mlp_dropouts(seq)]
+        at, k = 0, 0
+        for l, ((conv, bn), dp) in enumerate(zip(spec[4], drops)):
+            a = args.layer[l]
+            a.weight = params[k].data_ptr()
+            if bn is None:
+                a.bias, k = params[k + 1].data_ptr(), k + 2
+                continue
+            a.gamma, a.beta, k = params[k + 1].data_ptr(), params[k + 2].data_ptr(), k + 3
+            a.running_mean, a.running_var, a.momentum, a.eps, a.keep_scale = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.momentum, bn.eps, 1.0
+            if dp is not None and dp.p > 0:
+                a.mask, a.keep_scale = mask.data_ptr() + at, 1.0 / (1.0 - dp.p)
+                at += rows * conv.out_channels
+        nbytes = lib.s2d_roi_mlp_train_scratch_bytes(ctypes.byref(plan), rows)
+        ws = _roi_train_workspace(nbytes // 4, dev)
+        rcnn_cls = torch.empty((rows, 1), dtype=torch.float32, device=dev)
+        rcnn_reg = torch.empty((rows, 7), dtype=torch.float32, device=dev)
+        _lib.check(lib.s2d_roi_mlp_train_forward(ctypes.byref(plan), ctypes.byref(args), x.data_ptr(), rows, packed.data_ptr(), ws.data_ptr(), nbytes,
+                                                 rcnn_cls.data_ptr(), rcnn_reg.data_ptr(), st), "s2d_roi_mlp_train_forward")
+        # the call is counted as torch.batch_norm counts it: an ordinary in-place add, which moves the version `_mlp_images` keys its
+        # scale / shift vector on (the running statistics above were written through raw pointers)
+        torch._foreach_add_([bn.num_batches_tracked for _, bn in spec[4] if bn is not None], 1)
+        ctx.save_for_backward(x, mask, *params)
+        ctx.plan, ctx.args, ctx.ws, ctx.nbytes = plan, args, ws, nbytes
+        return rcnn_cls, rcnn_reg
+
+    @staticmethod
+    def backward(ctx, d_cls, d_reg):
+        x, mask, *params = ctx.saved_tensors
+        lib, dev, st = _device_args("roi_mlp_train", x)
+        rows = x.shape[0]
+        d_cls = torch.zeros((rows, 1), dtype=torch.float32, device=dev) if d_cls is None else _f32c(d_cls)
+        d_reg = torch.zeros((rows, 7), dtype=torch.float32, device=dev) if d_reg is None else _f32c(d_reg)
+        flat = torch.empty((sum(p.numel() for p in params),), dtype=torch.float32, device=dev)   # every element is written by its one owner
+        grads = [g.view(p.shape) for g, p in zip(flat.split([p.numel() for p in params]), params)]
+        args, k = ctx.args, 0
+        for l in range(ctx.plan.num_layers):
+            a = args.layer[l]
+            a.d_weight = grads[k].data_ptr()
+            if a.bias:
+                a.d_bias, k = grads[k + 1].data_ptr(), k + 2
+            else:
+                a.d_gamma, a.d_beta, k = grads[k + 1].data_ptr(), grads[k + 2].data_ptr(), k + 3
+        _lib.check(lib.s2d_roi_mlp_train_backward(ctypes.byref(ctx.plan), ctypes.byref(args), x.data_ptr(), rows, ctx.ws.data_ptr(), ctx.nbytes,
+                                                  d_cls.data_ptr(), d_reg.data_ptr(), st), "s2d_roi_mlp_train_backward")
+        return (None, None, None, None, *grads)
+
+
+def roi_mlp_train_fused(head, feats, masks=None):
+    """(rcnn_cls [R, 1], rcnn_reg [R, 7]) of feats [..., cin] through the TRAINING branch on the kernels of csrc/roi_mlp_train.hip, with a
+    grad_fn: gradients flow to every convolution weight, gamma, beta and the two final biases; the features get none (S2DError if they
+    require one).  Moves the running statistics and num_batches_tracked like the module's own training forward.  No host read and no
+    blocking call from the first forward launch to the last backward launch.  `masks`: one 0/1 tensor [R, width] per dropout site in the
+    order of `roi_mlp_train_sites`.  None: all sites' masks are drawn in ONE call from torch's current CUDA generator (`bernoulli_(1 - p)`
+    on one flat uint8 buffer), so the same seed gives the same masks - NOT the bits F.dropout would draw for that seed: the same
+    distribution from a different stream.  Raises with `head.train_mlp_reason(feats)` when the kernels do not apply: no fallback."""
+    reason, spec = head._train_mlp_check(feats)
+    if reason is not None:
+        raise _lib.S2DError(f"roi_mlp_train_fused: {reason}")
+    x = feats.detach().reshape(-1, feats.shape[-1])
+    x = x if x.is_contiguous() else x.contiguous()
+    rows = x.shape[0]
+    sites = [(w, p) for w, p in roi_mlp_train_sites(head) if p > 0]
+    if not sites:
+        mask = torch.empty((0,), dtype=torch.uint8, device=x.device)
+    elif masks is None:
+        if len({p for _, p in sites}) != 1:
+            raise _lib.S2DError("roi_mlp_train_fused: dropout sites of different ratios need caller-supplied masks")
+        mask = torch.empty((rows * sum(w for w, _ in sites),), dtype=torch.uint8, device=x.device).bernoulli_(1.0 - sites[0][1])
+    else:
+        given = [m for m, (_, p) in zip(masks, roi_mlp_train_sites(head)) if p > 0]
+        if len(masks) != len(roi_mlp_train_sites(head)) or any(tuple(m.shape) != (rows, w) for m, (w, _) in zip(given, sites)):
+            raise _lib.S2DError(f"roi_mlp_train_fused: masks of shapes {[(rows, w) for w, _ in roi_mlp_train_sites(head)]} expected")
+        mask = torch.cat([(m != 0).to(torch.uint8).reshape(-1) for m in given]).to(x.device)
+    params = [t for conv, bn in spec[4] for t in ((conv.weight, conv.bias) if bn is None else (conv.weight, bn.weight, bn.bias))]
+    return _RoiMlpTrain.apply(head, spec, x, mask, *params)
+
+
+class _RoiLoss(torch.autograd.Function):
+    """csrc/roi_mlp_train.hip: s2d_roi_loss_forward / _backward.  One launch each; the valid and foreground counts stay on the device."""
+    @staticmethod
+    def forward(ctx, cls, reg, labels, fg, target, code_weights, w_cls, w_reg):
+        lib, dev, st = _device_args("roi_loss", cls, reg, labels, fg, target)
+        out = torch.empty((4,), dtype=torch.float32, device=dev)
+        cw = (ctypes.c_float * 7)(*code_weights)
+        _lib.check(lib.s2d_roi_loss_forward(cls.data_ptr(), reg.data_ptr(), labels.data_ptr(), fg.data_ptr(), target.data_ptr(), cls.numel(), cw, w_cls,
+                                            w_reg, out.data_ptr(), st), "s2d_roi_loss_forward")
+        ctx.save_for_backward(cls, reg, labels, fg, target, out)
+        ctx.cfg = (cw, w_cls, w_reg)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_cls, g_reg):
+        cls, reg, labels, fg, target, out = ctx.saved_tensors
+        lib, dev, st = _device_args("roi_loss", cls)
+        zero = None
+        if g_cls is None or g_reg is None:
+            zero = torch.zeros((), dtype=torch.float32, device=dev)
+        g_cls, g_reg = (zero if g is None else _f32c(g) for g in (g_cls, g_reg))
+        d_cls, d_reg = torch.empty_like(cls), torch.empty_like(reg)
+        cw, w_cls, w_reg = ctx.cfg
+        _lib.check(lib.s2d_roi_loss_backward(cls.data_ptr(), reg.data_ptr(), labels.data_ptr(), fg.data_ptr(), target.data_ptr(), cls.numel(), cw, w_cls,
+                                             w_reg, out.data_ptr(), g_cls.data_ptr(), g_reg.data_ptr(), d_cls.data_ptr(), d_reg.data_ptr(), st),
+                   "s2d_roi_loss_backward")
+        return d_cls, d_reg, None, None, None, None, None, None
+
+
+def roi_loss_fused(rcnn_cls, rcnn_reg, cls_labels, reg_valid_mask, gt_of_rois, loss_cfg):
+    """`roi_loss_reference` on the kernels of csrc/roi_mlp_train.hip: (loss_cls, loss_reg), device scalars with a grad_fn; one launch
+    forward and one backward, no host read (the valid and foreground counts stay on the device).  fp32 CUDA tensors, code size 7."""
+    try:
+        code_weights, w_cls, w_reg = _loss_cfg(loss_cfg)
+    except NotImplementedError as e:
+        raise _lib.S2DError(f"roi_loss_fused: {e}")
+    if rcnn_reg.shape[-1] != 7 or len(code_weights) < 7 or rcnn_cls.numel() * 7 != rcnn_reg.numel() or rcnn_cls.numel() == 0:
+        raise _lib.S2DError(f"roi_loss_fused: rcnn_cls {tuple(rcnn_cls.shape)}, rcnn_reg {tuple(rcnn_reg.shape)} (one class, code size 7)")
+    if rcnn_cls.dtype != torch.float32 or rcnn_reg.dtype != torch.float32:
+        raise _lib.S2DError(f"roi_loss_fused: predictions of dtype {rcnn_cls.dtype} / {rcnn_reg.dtype}")
+    rows = rcnn_cls.numel()
+    cls = rcnn_cls.reshape(rows, 1)
+    reg = rcnn_reg.reshape(rows, 7)
+    with torch.no_grad():
+        labels, fg = _f32c(cls_labels.reshape(rows)), _f32c(reg_valid_mask.reshape(rows))
+        target = _f32c(gt_of_rois[..., 0:7].reshape(rows, 7))
+    return _RoiLoss.apply(cls if cls.is_contiguous() else cls.contiguous(), reg if reg.is_contiguous() else reg.contiguous(), labels, fg, target,
+                          code_weights[:7], w_cls, w_reg)
+
+
 class ProposalTargetLayer(nn.Module):
     """IoU-based sampling of the first stage's RoIs and their classification / regression labels
     (proposal_target_layer.py).  The random draws are the reference's (np.random.permutation / np.random.rand on the host,
@@ -478,6 +724,9 @@ class RoIHead(nn.Module):
         self.forward_ret_dict = None
         self.mlp_paths = {"fused": 0, "torch": 0}   # calls of forward() by the path their MLP took
         self._mlp_cache = None                      # the fused kernel's layer table, packed weight image and scale / shift vector
+        self.fused_training = False                 # opt-in: forward(training=True, device=True) and get_loss on csrc/roi_mlp_train.hip
+        self.train_paths = {"fused": 0, "torch": 0}   # calls of forward(training=True) by the path their MLP took
+        self.train_reason = None                    # why the last training forward with fused_training set kept the torch chain
 
     def assign_targets(self, batch_dict):
         """sampled RoIs + their ground-truth boxes encoded in the RoI's frame (roi_head_template.py:43-92)"""
@@ -534,8 +783,14 @@ class RoIHead(nn.Module):
 
     def get_loss(self, tb_dict=None):
         tb = {} if tb_dict is None else tb_dict
-        cls, c = self.get_box_cls_layer_loss(self.forward_ret_dict)
-        reg, r = self.get_box_reg_layer_loss(self.forward_ret_dict)
+        ret = self.forward_ret_dict
+        if ret.get("fused_training"):   # both losses in one launch, their backward in one more; the counts stay on the device
+            cls, reg = roi_loss_fused(ret["rcnn_cls"], ret["rcnn_reg"], ret["rcnn_cls_labels"], ret["reg_valid_mask"], ret["gt_of_rois"],
+                                      _cfg_get(self.model_cfg, "LOSS_CONFIG"))
+            c, r = {"rcnn_loss_cls": cls.detach()}, {"rcnn_loss_reg": reg.detach()}
+        else:
+            cls, c = self.get_box_cls_layer_loss(ret)
+            reg, r = self.get_box_reg_layer_loss(ret)
         tb.update(c); tb.update(r)
         total = cls + reg
         tb["rcnn_loss"] = total.item()
@@ -665,7 +920,55 @@ class RoIHead(nn.Module):
         runs the three nn.Sequential's through torch"""
         return self._mlp_check(feats)[0]
 
-    def _mlp_images(self, spec, dev):
+    def _train_mlp_check(self, feats):
+        """(reason | None, spec) for the training branch on csrc/roi_mlp_train.hip"""
+        cuda = torch.is_tensor(feats) and feats.is_cuda
+        return self._train_mlp_check_for(cuda, feats.dtype if cuda else None, feats.shape[-1] if cuda else None,
+                                         feats.numel() // max(feats.shape[-1], 1) if cuda else None, feats.device if cuda else None,
+                                         bool(cuda and feats.requires_grad))
+
+    def _train_mlp_check_for(self, cuda, dtype, channels, rows, device, feats_grad):
+        """`_train_mlp_check` from what it reads of the features (as `_mlp_check_for`)"""
+        if os.environ.get("S2D_ROI_MLP") == "0":
+            return "S2D_ROI_MLP=0", None
+        if not self.training:
+            return "the head is in eval mode (running statistics, no dropout)", None
+        spec = self._mlp_spec()
+        if isinstance(spec, str):
+            return spec, None
+        dp = float(_cfg_get(self.model_cfg, "DP_RATIO"))
+        if not dp < 1:
+            return f"DP_RATIO {dp} (below 1)", None
+        for conv, bn in spec[4]:
+            if bn is not None and (conv.bias is not None or bn.momentum is None or not bn.track_running_stats):
+                return "a hidden convolution with a bias, or a batch norm without momentum or running statistics", None
+        loss_cfg = _cfg_get(self.model_cfg, "LOSS_CONFIG", None)
+        if loss_cfg is not None and (_cfg_get(loss_cfg, "CLS_LOSS") != "BinaryCrossEntropy" or _cfg_get(loss_cfg, "REG_LOSS") != "L1"):
+            return f"{_cfg_get(loss_cfg, 'CLS_LOSS')} / {_cfg_get(loss_cfg, 'REG_LOSS')} losses (BinaryCrossEntropy and L1 only)", None
+        if not cuda:
+            return "the features are not a CUDA tensor (CPU tensor)", None
+        if dtype != torch.float32:
+            return f"feature dtype {dtype}", None
+        if channels != spec[0]:
+            return f"{channels} feature channels for a head of {spec[0]}", None
+        if not ROI_MLP_TRAIN_ROWS[0] <= rows <= ROI_MLP_TRAIN_ROWS[1]:
+            return f"{rows} rows ({ROI_MLP_TRAIN_ROWS[0]} .. {ROI_MLP_TRAIN_ROWS[1]}: batch statistics)", None
+        tensors = [t for conv, bn in spec[4] for t in ((conv.weight, conv.bias) if bn is None else
+                                                       (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))]
+        if any(t is None or t.device != device or t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+            return "parameters on another device or not fp32", None
+        if not torch.is_grad_enabled():
+            return "grad mode is disabled (the training branch exists for its backward)", None
+        if feats_grad:
+            return "the features require a gradient (the kernels give them none)", None
+        return None, spec
+
+    def train_mlp_reason(self, feats):
+        """None when forward(training=True, device=True) with `fused_training` set can run the MLP on csrc/roi_mlp_train.hip, else why it
+        keeps the three nn.Sequential's and autograd"""
+        return self._train_mlp_check(feats)[0]
+
+    def _mlp_images(self, spec, dev, affine=True):
         """(plan, packed weight image, scale / shift vector) of the fused MLP, cached on the head.  Keyed like dense2d.cached_pack on
         (data_ptr, _version) of every tensor that enters each of the two: an optimizer step, load_state_dict or an in-place edit of a
         running statistic rebuilds what it changed (and only that); dense2d.clear_pack_cache() - checkpoint.load - and
@@ -691,6 +994,8 @@ class RoIHead(nn.Module):
             ptrs = (ctypes.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
             _lib.check(lib.s2d_roi_mlp_pack(ctypes.byref(plan), ptrs, packed.data_ptr(), torch._C._cuda_getCurrentRawStream(dev.index)), "s2d_roi_mlp_pack")
             cache["w_key"], cache["packed"] = w_key, packed
+        if not affine:   # the training branch normalises with batch statistics
+            return plan, cache["packed"], None
         # (a training-mode batch norm moves its running statistics WITHOUT moving their version counters - torch.batch_norm does not declare
         # them as written - but it counts the call in num_batches_tracked with an ordinary in-place add: that counter is part of the key)
         a_key = key([t for conv, bn in chain for t in ((conv.bias,) if bn is None else
@@ -726,7 +1031,15 @@ class RoIHead(nn.Module):
             targets = self.assign_targets_device(batch_dict) if device else self.assign_targets(batch_dict)
             batch_dict["rois"], batch_dict["roi_labels"], batch_dict["roi_features"] = targets["rois"], targets["roi_labels"], targets["roi_features"]
         reason, spec = self._mlp_check(batch_dict["roi_features"]) if device and not training else ("training or the torch chain", None)
-        if reason is None:   # the whole eval MLP in one launch (csrc/roi_mlp.hip)
+        fused_training = False
+        if training:
+            self.train_reason = self.train_mlp_reason(batch_dict["roi_features"]) if device and self.fused_training else None
+            fused_training = device and self.fused_training and self.train_reason is None
+            self.train_paths["fused" if fused_training else "torch"] += 1
+        if fused_training:   # batch statistics, dropout and a backward on csrc/roi_mlp_train.hip
+            rcnn_cls, rcnn_reg = roi_mlp_train_fused(self, batch_dict["roi_features"])
+            targets["fused_training"] = True
+        elif reason is None:   # the whole eval MLP in one launch (csrc/roi_mlp.hip)
             self.mlp_paths["fused"] += 1
             rcnn_cls, rcnn_reg = self._mlp_fused(batch_dict["roi_features"], spec)
         else:
