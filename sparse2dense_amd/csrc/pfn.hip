@@ -515,8 +515,8 @@ __global__ __launch_bounds__(256) void pfn2_bwd_kernel(const float *__restrict__
                 h2 = fmaf(wa[4 * q + 3], xv[q].w, h2);
             }
             const float rest = fmaf(b2, h2, d2);
-            // row n: ONE of the empty rows holds an arg-2 maximum, all of them carry the b / d terms
-            const float dh2 = t == h.n ? fmaf(a2, bi == t ? go : 0.f, (float)(g.slots - h.n) * rest) : fmaf(a2, bi == t ? go : 0.f, rest);
+            // row n: ONE of the empty rows holds an arg-2 maximum (whichever of them the argmax names), all of them carry the b / d terms
+            const float dh2 = t == h.n ? fmaf(a2, bi >= t ? go : 0.f, (float)(g.slots - h.n) * rest) : fmaf(a2, bi == t ? go : 0.f, rest);
             sdh2 += dh2;
 #pragma unroll
             for (int q = 0; q < PFN2_C1 / 4; ++q) {
