@@ -232,7 +232,8 @@ def _pack_weights(weight, transpose_flip):
 
 
 BN_BWD_FOLD = 0   # (read from the environment below)
-STATS = {"bn_bwd_folded": 0, "bn_bwd_reduced": 0}   # batch-norm backward passes that took the conv epilogue's sums / their own reduction pass
+STATS = {"bn_bwd_folded": 0, "bn_bwd_reduced": 0,   # batch-norm backward passes that took the conv epilogue's sums / their own reduction pass
+         "bn_fwd_folded": 0}                          # training-mode forwards that took the producer's epilogue statistics (no pass over x)
 
 
 def _bn_src_of(x):
@@ -241,6 +242,26 @@ def _bn_src_of(x):
     if src is None or src[0].shape != x.shape or src[3] != x._version or (src[2] == 2 and int(BN_BWD_FOLD) < 2):
         return None
     return src
+
+
+def _tag_bn_partial(y, partial):
+    """y is a producer's fresh output and `partial` the per-tile (sum, sum of squares) rows its epilogue wrote: read by the batch norm that
+    follows (_bn_partial_of) - valid only while y still holds what the kernel wrote, hence the version stamp (same scheme as _s2d_bn_src)"""
+    y._s2d_bn_partial = partial
+    y._s2d_bn_partial_version = y._version
+    return y
+
+
+def _bn_partial_of(x, c):
+    """the epilogue statistics a producer left on x, if x still is that tensor: an in-place operation on x since keeps the Python object
+    and its attributes but not the values the rows were summed over.  (A list without a stamp was attached by the caller by hand.)"""
+    partial = getattr(x, "_s2d_bn_partial", None)
+    if partial is None or partial.shape[2] != c:
+        return None
+    stamp = getattr(x, "_s2d_bn_partial_version", None)
+    if stamp is not None and stamp != x._version:
+        return None
+    return partial
 
 
 def _tag_bn_bwd(dx, partial):
@@ -435,7 +456,7 @@ class Conv3x3(nn.Conv2d):
             src = _bn_src_of(x) if torch.is_grad_enabled() else None
             if self.emit_bn_stats and self.training and torch.is_grad_enabled():
                 y, partial = _Conv3x3Fn.apply(x, self.weight, self.bias, pad, self.stride[0], True, src)
-                y._s2d_bn_partial = partial   # read (forward pass only) by the FastBatchNorm2d that follows
+                _tag_bn_partial(y, partial)   # read (forward pass only) by the FastBatchNorm2d that follows
                 return y
             return _Conv3x3Fn.apply(x, self.weight, self.bias, pad, self.stride[0], False, src)
         if self.absorbed_pad:
@@ -644,7 +665,7 @@ class Conv1x1(nn.Conv2d):
             src = _bn_src_of(x) if torch.is_grad_enabled() else None
             if self.emit_bn_stats and self.training and torch.is_grad_enabled():
                 y, partial = _Conv1x1Fn.apply(x, self.weight, self.bias, True, src)
-                y._s2d_bn_partial = partial   # read (forward pass only) by the FastBatchNorm2d that follows
+                _tag_bn_partial(y, partial)   # read (forward pass only) by the FastBatchNorm2d that follows
                 return y
             return _Conv1x1Fn.apply(x, self.weight, self.bias, False, src)
         return super().forward(x)
@@ -778,7 +799,7 @@ class Conv2x2S2(nn.Conv2d):
         if self._hip_ok(x):
             if self.emit_bn_stats and self.training and torch.is_grad_enabled():
                 y, partial = _Conv2x2S2Fn.apply(x, self.weight, self.bias, True)
-                y._s2d_bn_partial = partial
+                _tag_bn_partial(y, partial)
                 return y
             return _Conv2x2S2Fn.apply(x, self.weight, self.bias, False)
         return super().forward(x)
@@ -941,6 +962,8 @@ class _BNRowFn(torch.autograd.Function):
             fp, rb = fin.data_ptr(), 4 * c
             if track:   # the finalize kernels below update the running statistics through raw pointers (no version bump): see the eval cache
                 module._s2d_stats_epoch = getattr(module, "_s2d_stats_epoch", 0) + 1
+            if partial is not None:
+                STATS["bn_fwd_folded"] += 1
             if partial is not None and not sync:   # statistics pass already done in the producing conv's epilogue
                 pws = ws
                 if lib.s2d_bn_partials_sum_workspace_bytes(partial.shape[0], c) > ws.numel():   # long list (sparse conv tiles): two stages
@@ -1092,9 +1115,7 @@ class FastBatchNorm2d(nn.BatchNorm2d):
         training = self.training or not self.track_running_stats
         sync = training and _dist_sync()
         if self._hip_ok(x):
-            partial = getattr(x, "_s2d_bn_partial", None) if training else None
-            if partial is not None and partial.shape[2] != self.num_features:
-                partial = None
+            partial = _bn_partial_of(x, self.num_features) if training else None
             return _BNRowFn.apply(x, self.weight, self.bias, None, relu, self.eps, sync, self, training, partial, out)
         assert out is None, "FastBatchNorm2d(out=...) needs the HIP path"
         if sync and x.is_cuda:
@@ -1299,7 +1320,7 @@ class ConvT4x4S2(nn.ConvTranspose2d):
         if output_size is None and self._hip_ok(x):
             if self.emit_bn_stats and self.training and torch.is_grad_enabled():
                 y, partial = _ConvT4x4S2Fn.apply(x, self.weight, self.bias, True)
-                y._s2d_bn_partial = partial
+                _tag_bn_partial(y, partial)
                 return y
             return _ConvT4x4S2Fn.apply(x, self.weight, self.bias, False)
         return super().forward(x, output_size)

@@ -390,6 +390,19 @@ class PointwiseConv3d(nn.Conv3d):
         return super().forward(x)
 
 
+def bn_stats_of(x, c):
+    """the [sum | sum of squares] per channel a producer's epilogue left on x (`_s2d_bn_stats`), if x still is that tensor: a producer that
+    stamps the tag with its output's version (ConvTranspose3dK4S2) has it dropped after an in-place operation on x.  (A list without a
+    stamp was attached by the caller by hand.)"""
+    stats = getattr(x, "_s2d_bn_stats", None)
+    if stats is None or stats.numel() != 2 * c:
+        return None
+    stamp = getattr(x, "_s2d_bn_stats_version", None)
+    if stamp is not None and stamp != x._version:
+        return None
+    return stats
+
+
 class ConvTranspose3dK4S2(nn.ConvTranspose3d):
     """nn.ConvTranspose3d(cin, cout, 4, 2, 1).  `bf16_compute` (set by the detector in its bf16 mode) selects the matrix-core
     kernels: operands rounded to bf16, fp32 accumulate, fp32 NCDHW tensors."""
@@ -404,6 +417,7 @@ class ConvTranspose3dK4S2(nn.ConvTranspose3d):
             if self.emit_bn_stats and self.training and torch.is_grad_enabled():
                 y, stats = _ConvT3dFn.apply(x, self.weight, self.bias, self.bf16_compute, True, self.out_bf16)
                 y._s2d_bn_stats = stats
+                y._s2d_bn_stats_version = y._version   # (the sums describe y as the kernel wrote it: FastBatchNorm3d drops them after an in-place op)
                 return y
             return _ConvT3dFn.apply(x, self.weight, self.bias, self.bf16_compute)
         return super().forward(x, output_size)
@@ -530,9 +544,10 @@ class FastBatchNorm3d(nn.BatchNorm3d):
         sync = training and _collective.sync_on()
         if _hip_ok(x) and x.dim() >= 3 and x[0, 0].numel() % 4 == 0 and self.affine and x.shape[0] * x.shape[1] <= 65535 \
                 and self.momentum is not None:
-            stats = getattr(x, "_s2d_bn_stats", None) if training else None
-            if stats is not None and stats.numel() != 2 * self.num_features:
-                stats = None
+            stats = bn_stats_of(x, self.num_features) if training else None
+            if stats is not None:
+                from .dense2d import STATS
+                STATS["bn_fwd_folded"] += 1
             return _BNChannelMajorFn.apply(x, self.weight, self.bias, self.fused_relu, self.eps, sync, self, training, stats)
         if sync and x.is_cuda:   # inputs the channel-major kernels do not cover still synchronise (as FastBatchNorm2d does)
             import torch.distributed as dist

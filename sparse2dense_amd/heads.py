@@ -25,6 +25,7 @@ from torch import nn
 from . import center_predict
 from .dcn import DeformConv
 from .dense2d import Conv3x3, FastBatchNorm2d, SmallConv3x3, fuse_bn_relu
+from .dense3d import bn_stats_of as _bn_stats_of
 from .registry import HEADS, LOSSES
 
 
@@ -643,7 +644,7 @@ def pcr_level_norm(y, bn, mask_conv, offset_conv, coors, feats, next_conv=None):
     holder = []
     out = _PcrLevelNormFn.apply(y, bn.weight, bn.bias, mask_conv.weight, mask_conv.bias, offset_conv.weight, offset_conv.bias, coors,
                                 feats.float(), None if next_conv is None else next_conv.weight, None if next_conv is None else next_conv.bias,
-                                bn, bool(getattr(next_conv, "bf16_compute", False)), getattr(y, "_s2d_bn_stats", None), holder)
+                                bn, bool(getattr(next_conv, "bf16_compute", False)), _bn_stats_of(y, bn.num_features), holder)
     if holder and out[2] is not None:
         out[2]._s2d_bn_stats = holder[0]   # read by the FastBatchNorm3d that follows the 1x1x1 conv (dense3d.FastBatchNorm3d.forward)
     return out
@@ -732,8 +733,7 @@ def upsample_level(ct, x, bn, mask_conv, offset_conv, coors, feats, next_conv=No
     pre = (None, None, None, None)
     if pre_bn is not None:
         assert y16 and pre_bn.training and pre_bn.affine and getattr(pre_bn, "fused_relu", False) and pre_bn.momentum is not None
-        stats = getattr(x, "_s2d_bn_stats", None)
-        pre = (pre_bn.weight, pre_bn.bias, pre_bn, stats if stats is not None and stats.numel() == 2 * pre_bn.num_features else None)
+        pre = (pre_bn.weight, pre_bn.bias, pre_bn, _bn_stats_of(x, pre_bn.num_features))
     out = _UpsampleLevelFn.apply(x, ct.weight, ct.bias, bn.weight, bn.bias, mask_conv.weight, mask_conv.bias, offset_conv.weight, offset_conv.bias,
                                  coors, feats.float(), None if next_conv is None else next_conv.weight, None if next_conv is None else next_conv.bias,
                                  bn, bool(getattr(next_conv, "bf16_compute", False)), holder, bool(y16), *pre, bool(z16))

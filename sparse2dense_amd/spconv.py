@@ -255,7 +255,8 @@ class SparseConvolution(SparseModule):
         if self.emit_bn_stats and self.training and torch.is_grad_enabled() and feats.dtype == torch.bfloat16 and rb.n_out > 0:
             feats, partial = _SparseConvFn.apply(feats, self.weight, self.bias, rb, True)
             if partial.numel():
-                feats._s2d_bn_partial = partial   # read (forward pass only) by the FeatureBatchNorm1d that follows
+                from .dense2d import _tag_bn_partial
+                _tag_bn_partial(feats, partial)   # read (forward pass only) by the FeatureBatchNorm1d that follows
         else:
             feats = _SparseConvFn.apply(feats, self.weight, self.bias, rb)
         if self.subm:
@@ -385,11 +386,11 @@ class FeatureBatchNorm1d(nn.BatchNorm1d):
                 return _EmptySyncFn.apply(x, 2 * self.num_features + 1, 2 * self.num_features)
             return x
         if x.dtype == torch.bfloat16:   # bf16-storage stack: the row-major bf16 kernels (also used by the BEV neck)
-            from .dense2d import _BNRowFn
+            from .dense2d import _BNRowFn, _bn_partial_of
             if self.num_features % 8:
                 raise RuntimeError("FeatureBatchNorm1d: bf16 features need a channel count that is a multiple of 8")
-            partial = getattr(x, "_s2d_bn_partial", None) if use_batch_stats else None
-            if partial is not None and (partial.shape[2] != self.num_features or not x.is_contiguous()):
+            partial = _bn_partial_of(x, self.num_features) if use_batch_stats else None
+            if partial is not None and not x.is_contiguous():
                 partial = None
             return _BNRowFn.apply(x.contiguous(), self.weight, self.bias, None if residual is None else residual.contiguous(),
                                   relu, self.eps, _dist_on() and use_batch_stats, self, use_batch_stats, partial)
